@@ -17,9 +17,13 @@ A "step" processes one global batch (--batch images). At world > 1 the
 global batch is split into --micro-batch-sized pipeline items so the
 chain stays full (the reference streams single images through its node
 chain, test/test.py:20-23,47-49; micro-batches are the throughput-viable
-version of that operating point). After the timed region a short
-serialized pass measures true per-item end-to-end latency (feed at rank0
--> result back at rank0, host-synchronized), reported as latency_ms.
+version of that operating point).
+
+A plain run sets up, warms up, times --steps steps and prints the result
+line. With --full, a short serialized pass after the timed region also
+measures true per-item end-to-end latency (feed at rank0 -> result back
+at rank0, host-synchronized), reported as latency_ms (null otherwise).
+--dump-outputs DIR writes the last timed step's outputs as DIR/output.npy.
 """
 
 import argparse
@@ -71,9 +75,15 @@ def parse_args(argv=None):
     ap.add_argument("--no-dual-rail", dest="dual_rail",
                     action="store_false")
     ap.add_argument("--no-return-results", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline "
+                         "figure (the serialized latency pass)")
     ap.add_argument("--latency-items", type=int, default=32,
-                    help="serialized items for the post-run latency "
-                         "measurement (0 = skip)")
+                    help="serialized items for the --full post-run "
+                         "latency measurement (0 = skip)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as "
+                         "DIR/output.npy (float32)")
     ap.add_argument("--calibration", default=None, metavar="JSON",
                     help="per-layer measured-cost file for auto cuts "
                          "(tools/calibrate.py); default: use the "
@@ -175,6 +185,16 @@ def worker(args):
     def collect(k, y):
         sink["last"] = (k, y.shape)
 
+    # --dump-outputs: keep the items of the last timed step (the slot a
+    # ring hands to collect is reused, so clone; one step's logits only)
+    kept = {}
+    first_kept = (args.steps - 1) * per_step
+
+    def collect_kept(k, y):
+        sink["last"] = (k, y.shape)
+        if k >= first_kept:
+            kept[k] = y.clone()
+
     def barrier_sync():
         dist.barrier()
         if args.device == "cuda":
@@ -238,7 +258,8 @@ def worker(args):
 
     # ---- timed region: exactly --steps global batches
     t0 = time.perf_counter()
-    pipe.run(args.steps * per_step, feed=feed, collect=collect)
+    pipe.run(args.steps * per_step, feed=feed,
+             collect=collect_kept if args.dump_outputs else collect)
     barrier_sync()
     t1 = time.perf_counter()
 
@@ -254,11 +275,26 @@ def worker(args):
 
     timed_stats = copy.copy(pipe.stats)   # before the latency pass runs
 
-    # ---- untimed: serialized per-item end-to-end latency (rank0 feed ->
-    # rank0 result, host-synced per item; the reference's batch-1
+    # ---- --dump-outputs: what the last timed step handed to collect, on
+    # the rank that received it (rank 0, or the last rank under
+    # --no-return-results), in item order
+    if kept:
+        import numpy as np
+
+        y = torch.cat([kept[k] for k in sorted(kept)]).float().cpu().numpy()
+        cap = (64 << 20) // 4
+        if y.size > cap:   # fixed seeded sample of an oversized output
+            idx = np.sort(np.random.default_rng(0).choice(
+                y.size, cap, replace=False))
+            y = y.reshape(-1)[idx]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "output.npy"), y)
+
+    # ---- --full, untimed: serialized per-item end-to-end latency (rank0
+    # feed -> rank0 result, host-synced per item; the reference's batch-1
     # streaming protocol operating point, test/test.py:47-49)
     lat = None
-    L = args.latency_items
+    L = args.latency_items if args.full else 0
     if L > 0 and (world == 1 or not args.no_return_results):
         lat_ms = []
         t_feed = {}

@@ -182,6 +182,7 @@ def test_bench_torchrun_two_ranks_cpu():
     for key, typ in schema.items():
         assert key in d and isinstance(d[key], typ), (key, d.get(key))
     assert "vs_baseline" in d            # null allowed
+    assert d["latency_ms"] is None       # latency pass runs under --full
     assert d["scaling"] in ("weak", "strong")
     assert d["data"] == "synthetic" and d["higher_is_better"] is True
     for key in ("model", "global_batch", "parallelism"):
@@ -432,18 +433,23 @@ def test_var_ring_deferred_interleave_gloo():
         assert e < 1e-6, f"deferred interleave corrupted payloads: {e}"
 
 
-def test_bench_self_spawn_two_ranks_cpu():
+def test_bench_self_spawn_two_ranks_cpu(tmp_path):
     """The driver's bare `bench.py --gpus N` form: bench self-spawns N
-    ranks via mp.spawn (no torchrun) and prints one JSON line."""
+    ranks via mp.spawn (no torchrun) and prints one JSON line. --full
+    adds the serialized latency pass; --dump-outputs writes the last
+    timed step's softmax rows (both micro-batches of the step)."""
     import json
     import subprocess
     import sys
+
+    import numpy as np
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run(
         [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
          "--device", "cpu", "--batch", "4", "--micro-batch", "2",
-         "--steps", "2", "--warmup", "1", "--latency-items", "1"],
+         "--steps", "2", "--warmup", "1", "--full", "--latency-items", "1",
+         "--dump-outputs", str(tmp_path / "out")],
         capture_output=True, text=True, timeout=420, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -452,6 +458,9 @@ def test_bench_self_spawn_two_ranks_cpu():
     assert d["n_gpus"] == 2 and d["steps"] == 2
     assert d["config"]["parallelism"] == "pp2"
     assert d["latency_ms"]["items"] == 1
+    y = np.load(tmp_path / "out" / "output.npy")
+    assert y.dtype == np.float32 and y.shape == (4, 1000)
+    assert y.min() >= 0.0 and np.abs(y.sum(axis=-1) - 1.0).max() < 1e-4
 
 
 def test_bench_dual_rail_watchdog_fallback_cpu():
