@@ -297,6 +297,51 @@ Tensor conv1x1_prebn(Tensor x, Tensor w, Tensor scale, Tensor bias,
     return out;
 }
 
+std::tuple<Tensor, Tensor> conv1x1_chain(
+    Tensor x, Tensor w3, c10::optional<Tensor> s3, c10::optional<Tensor> b3,
+    Tensor res, bool relu3, Tensor w1, c10::optional<Tensor> s1,
+    c10::optional<Tensor> b1, bool relu1, int64_t mode,
+    int64_t max_blocks) {
+    // y = act3(conv1x1(x, w3)*s3+b3 + res); a2 = act1(conv1x1(y, w1)*s1+b1)
+    // mode 0: fused kernel where the launcher's measured policy says so;
+    // 1: fused wherever an instantiation exists; 2: always two launches.
+    check_bf16(x, "x");
+    check_bf16(w3, "w3");
+    check_bf16(w1, "w1");
+    check_bf16(res, "res");
+    TORCH_CHECK(x.dim() == 4 && w3.dim() == 4 && w1.dim() == 4 &&
+                w3.size(1) == 1 && w3.size(2) == 1 && w1.size(1) == 1 &&
+                w1.size(2) == 1, "conv1x1_chain wants NHWC x, 1x1 weights");
+    TORCH_CHECK(mode >= 0 && mode <= 2, "mode must be 0, 1 or 2");
+    int NB = x.size(0), H = x.size(1), W = x.size(2), K1 = x.size(3);
+    int N1 = w3.size(0), N2 = w1.size(0);
+    TORCH_CHECK(w3.size(3) == K1 && w1.size(3) == N1, "channel mismatch");
+    TORCH_CHECK(res.dim() == 4 && res.size(0) == NB && res.size(1) == H &&
+                res.size(2) == W && res.size(3) == N1,
+                "res must match the expand output");
+    TORCH_CHECK((!s3 || s3->numel() == N1) && (!b3 || b3->numel() == N1) &&
+                (!s1 || s1->numel() == N2) && (!b1 || b1->numel() == N2),
+                "scale/bias length must equal the conv's Cout");
+    long M = (long)NB * H * W;
+    TORCH_CHECK(M < (1LL << 31), "M too large");
+    if (mode != 2 && K1 % 64 == 0 && N1 % 64 == 0 && N2 % 64 == 0) {
+        auto y = at::empty({NB, H, W, N1}, x.options());
+        auto a2 = at::empty({NB, H, W, N2}, x.options());
+        if (defer_hip::launch_conv1x1_chain(
+                bptr(x), bptr(w3), fptr_opt(s3, "s3", ones_buf(), N1),
+                fptr_opt(b3, "b3", zeros_buf(), N1), bptr(res),
+                bptr_mut(y), relu3, bptr(w1),
+                fptr_opt(s1, "s1", ones_buf(), N2),
+                fptr_opt(b1, "b1", zeros_buf(), N2), bptr_mut(a2), relu1,
+                (int)M, K1, N1, N2, mode == 1, (int)max_blocks,
+                cur_stream()))
+            return {y, a2};
+    }
+    auto y = conv2d_bn_act(x, w3, s3, b3, res, 1, 0, relu3);
+    auto a2 = conv2d_bn_act(y, w1, s1, b1, c10::nullopt, 1, 0, relu1);
+    return {y, a2};
+}
+
 Tensor bn_act(Tensor x, Tensor scale, Tensor bias, bool relu) {
     check_bf16(x, "x");
     int C = x.size(-1);
@@ -555,6 +600,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("w"), py::arg("scale"), py::arg("bias"),
           py::arg("out_scale") = py::none(),
           py::arg("out_bias") = py::none());
+    m.def("conv1x1_chain", &conv1x1_chain, py::arg("x"), py::arg("w3"),
+          py::arg("s3"), py::arg("b3"), py::arg("res"), py::arg("relu3"),
+          py::arg("w1"), py::arg("s1"), py::arg("b1"), py::arg("relu1"),
+          py::arg("mode") = 0, py::arg("max_blocks") = 0);
     m.def("add_act", &add_act);
     m.def("relu", &relu);
     m.def("softmax", &softmax);

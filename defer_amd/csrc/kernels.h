@@ -50,6 +50,21 @@ void launch_gemm_prebn(const void* x, const void* w, const float* ps,
                        const void* zbuf, void* out, int M, int K,
                        int Cout, hipStream_t s);
 
+// chained 1x1 expand + residual + act -> next 1x1 reduce (chain.hip):
+//   y  = act3((x[M,K1] @ w3[N1,K1]^T) * s3 + b3 + res[M,N1])
+//   a2 = act1((y @ w1[N2,N1]^T) * s1 + b1)
+// both bit-identical to two GEMM-mode launch_conv_igemm calls. Returns
+// false (nothing launched) when the shape has no instantiation or, with
+// force == false, is not in the measured-win policy table. max_blocks
+// caps the grid (0 = policy) so small M can exercise several m-tiles
+// per block.
+bool launch_conv1x1_chain(const void* x, const void* w3, const float* s3,
+                          const float* b3, const void* res, void* y,
+                          bool relu3, const void* w1, const float* s1,
+                          const float* b1, void* a2, bool relu1, int M,
+                          int K1, int N1, int N2, bool force,
+                          int max_blocks, hipStream_t s);
+
 void launch_bn_act(const void* x, const float* scale, const float* bias,
                    void* y, long total8, int c8, bool relu, hipStream_t s);
 void launch_add_act(const void* a, const void* b, void* y, long total8,

@@ -10,6 +10,7 @@ On CPU, ops use the fp32 PyTorch reference implementations (tests and the
 no-GPU plumbing config).
 """
 
+import os
 from typing import Optional
 
 import torch
@@ -75,6 +76,38 @@ def conv1x1_prebn(x, w, scale, bias, out_scale=None, out_bias=None):
             y = _ref.batchnorm_apply(y, out_scale, out_bias, "relu")
         return y
     return m.conv1x1_prebn(x, w, scale, bias, out_scale, out_bias)
+
+
+# A/B switch for the chained expand->reduce kernel (mirrors
+# DEFER_CONV_VARIANT): unset = the launcher's measured policy, "0" = always
+# two launches, "force" = fused wherever an instantiation exists.
+_CHAIN_MODES = {None: 0, "": 0, "force": 1, "0": 2}
+_chain_env = os.environ.get("DEFER_CONV_CHAIN")
+if _chain_env not in _CHAIN_MODES:
+    raise ValueError(
+        f"DEFER_CONV_CHAIN={_chain_env!r}: expected unset, '0' or 'force'")
+_CHAIN_MODE = _CHAIN_MODES[_chain_env]
+
+
+def conv1x1_chain(x, w3, s3, b3, residual, act3, w1, s1, b1, act1,
+                  mode=None, max_blocks=0):
+    """Bottleneck boundary pair in one call:
+
+        y  = act3(conv1x1(x, w3)*s3 + b3 + residual)
+        a2 = act1(conv1x1(y, w1)*s1 + b1)
+
+    Returns (y, a2), identical to two conv2d_bn_act calls. On GPU the
+    chain kernel (csrc/chain.hip) keeps each y tile in LDS for the second
+    GEMM, so y is written once and never read back. mode: 0 = policy,
+    1 = fused wherever legal, 2 = two launches; None = DEFER_CONV_CHAIN."""
+    m = _backend(x)
+    if m is None:
+        y = _ref.conv2d_bn_act(x, w3, s3, b3, 1, 0, act3, residual)
+        a2 = _ref.conv2d_bn_act(y, w1, s1, b1, 1, 0, act1, None)
+        return y, a2
+    return m.conv1x1_chain(x, w3, s3, b3, residual, act3 == "relu", w1, s1,
+                           b1, act1 == "relu",
+                           _CHAIN_MODE if mode is None else mode, max_blocks)
 
 
 def batchnorm_apply(x, scale, bias, act="none"):

@@ -9,6 +9,11 @@ collapses into one kernel launch: y = conv(x, residual=skip, act=act).
 This removes one full read+write round trip of the conv output per
 residual block (16 blocks in ResNet50 — ~9% of forward time unfused).
 
+A second pass, fuse_expand_reduce, chains that fused node with the next
+block's 1x1 conv1 (ops.conv1x1_chain): add_k is the widest tensor of the
+block and conv1 reads it straight back, so one kernel computes both and
+add_k is never re-read.
+
 Cut-point names are preserved: the fused node takes the AddAct node's
 name, so partition boundaries at `add_N` (test/test.py:18) still resolve.
 Fusion happens per stage AFTER partitioning.
@@ -75,4 +80,81 @@ def fuse_residual_adds(graph: LayerGraph) -> LayerGraph:
                 nodes.append(n)
             continue
         nodes.append(n)
+    return LayerGraph(nodes, output=graph.output)
+
+
+class ChainedExpandReduce(nn.Module):
+    """add_k = act(conv3(x) + skip) and the next block's conv1(add_k) in
+    one call; returns the (add_k, conv1) tuple. The original modules stay
+    referenced (not copied), so parameters are shared with the unfused
+    graph."""
+
+    def __init__(self, expand: FusedConvAddAct, reduce: ConvBNAct):
+        super().__init__()
+        self.expand = expand
+        self.reduce = reduce
+
+    def forward(self, x, residual):
+        from defer_amd import ops
+
+        c3, c1 = self.expand.conv, self.reduce
+        return ops.conv1x1_chain(
+            x, c3.weight.to(x.dtype), c3.scale, c3.bias, residual,
+            self.expand.act, c1.weight.to(x.dtype), c1.scale, c1.bias,
+            c1.act)
+
+
+class _Pick(nn.Module):
+    """Select one item of a tuple-valued node (nodes carry one value)."""
+
+    def __init__(self, index: int):
+        super().__init__()
+        self.index = index
+
+    def forward(self, t):
+        return t[self.index]
+
+    def extra_repr(self):
+        return f"item {self.index}"
+
+
+def _is_pointwise(c: ConvBNAct) -> bool:
+    return c.kernel == 1 and c.stride == 1 and c.padding == 0
+
+
+def fuse_expand_reduce(graph: LayerGraph) -> LayerGraph:
+    """Rewrite FusedConvAddAct(1x1) -> ConvBNAct(1x1, single input) pairs
+    into one ChainedExpandReduce node plus two picks that keep the
+    original node names. add_k may have other consumers and may be the
+    graph output; a conv1 outside this graph is simply not matched."""
+    consumers = {}
+    for n in graph.nodes:
+        for p in n.inputs:
+            consumers.setdefault(p, []).append(n)
+
+    partner = {}                       # add_k name -> conv1 node
+    for n in graph.nodes:
+        if not (isinstance(n.layer, FusedConvAddAct)
+                and _is_pointwise(n.layer.conv)):
+            continue
+        for c in consumers.get(n.name, []):
+            if (isinstance(c.layer, ConvBNAct) and _is_pointwise(c.layer)
+                    and c.inputs == [n.name] and not c.kwargs):
+                partner[n.name] = c
+                break
+    taken = {c.name for c in partner.values()}
+
+    nodes: List[GraphNode] = []
+    for n in graph.nodes:
+        if n.name in taken:
+            continue                   # emitted right after its add_k
+        c = partner.get(n.name)
+        if c is None:
+            nodes.append(n)
+            continue
+        pair = n.name + "__chain"
+        nodes.append(GraphNode(pair, ChainedExpandReduce(n.layer, c.layer),
+                               list(n.inputs), dict(n.kwargs)))
+        nodes.append(GraphNode(n.name, _Pick(0), [pair]))
+        nodes.append(GraphNode(c.name, _Pick(1), [pair]))
     return LayerGraph(nodes, output=graph.output)

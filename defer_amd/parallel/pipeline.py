@@ -62,12 +62,16 @@ class StageExecutor:
     _capture_lock = threading.Lock()
 
     def __init__(self, stage: GraphModel, device, dtype: torch.dtype,
-                 use_graph: bool = False, fuse: bool = True):
+                 use_graph: bool = False, fuse: bool = True,
+                 chain: bool = True):
         if fuse:
-            from defer_amd.parallel.fusion import fuse_residual_adds
+            from defer_amd.parallel.fusion import (fuse_expand_reduce,
+                                                   fuse_residual_adds)
 
-            stage = GraphModel(fuse_residual_adds(stage.graph),
-                               name=stage.model_name)
+            g = fuse_residual_adds(stage.graph)
+            if chain:
+                g = fuse_expand_reduce(g)
+            stage = GraphModel(g, name=stage.model_name)
         self.model = stage
         self.device = torch.device(device)
         self.dtype = dtype
