@@ -6,8 +6,10 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include <cstdlib>
 #include <functional>
 #include <mutex>
+#include <string>
 #include <unordered_map>
 
 #include "kernels.h"
@@ -29,6 +31,26 @@ void check_bf16(const Tensor& t, const char* name) {
     TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " must be bf16");
     TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
+
+// dtype dispatch for the op entry points: true = the fp32 launchers,
+// false = the bf16 ones; every other dtype raises.
+bool is_f32(const Tensor& t, const char* name) {
+    if (t.scalar_type() == at::kBFloat16) return false;
+    TORCH_CHECK(t.scalar_type() == at::kFloat, name,
+                " must be bf16 or fp32");
+    return true;
+}
+
+void check_f32(const Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+    TORCH_CHECK(t.scalar_type() == at::kFloat, name,
+                " must be fp32 like x (mixed dtypes)");
+    TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+    TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0, name,
+                " must be 16-byte aligned");
+}
+
+const float* f32ptr(const Tensor& t) { return t.data_ptr<float>(); }
 
 // 16B zero source for OOB global_load_lds lanes, one per process
 const void* zero_buf() {
@@ -99,9 +121,134 @@ const float* fptr_opt(const c10::optional<Tensor>& t, const char* name,
     return t->data_ptr<float>();
 }
 
+// ---- fp32 path ----
+
+// A/B switch for the fp32 conv tile (mirrors DEFER_CONV_VARIANT): unset =
+// the launcher's heuristic, "128x128" / "128x64" force one tile.
+int conv_f32_tile() {
+    static int tile = [] {
+        const char* e = std::getenv("DEFER_CONV_F32_TILE");
+        if (!e || !*e) return 0;
+        std::string v(e);
+        TORCH_CHECK(v == "128x128" || v == "128x64",
+                    "DEFER_CONV_F32_TILE: expected unset, '128x128' or "
+                    "'128x64'");
+        return v == "128x128" ? 1 : 2;
+    }();
+    return tile;
+}
+
+// nullable fp32[n] scale/bias for the fp32 kernels (null = 1 / 0)
+const float* f32_vec_opt(const c10::optional<Tensor>& t, const char* name,
+                         int64_t n) {
+    if (!t) return nullptr;
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat &&
+                t->is_contiguous() && t->numel() == n &&
+                (uintptr_t)t->data_ptr() % 16 == 0,
+                name, " must be a contiguous GPU fp32[Cout]");
+    return t->data_ptr<float>();
+}
+
+// shared tail of the fp32 conv / linear entry points; x is [.., Cin]
+// with Cin % 4 == 0 here
+void run_conv_f32(const Tensor& x, const Tensor& w, const float* scale,
+                  const float* bias, const c10::optional<Tensor>& res,
+                  Tensor& out, long M, int H, int W, int Cin, int OH, int OW,
+                  int R, int S, int stride, int pad, bool relu) {
+    int Cout = (int)out.size(-1);
+    TORCH_CHECK(M < (1LL << 31), "M too large");
+    TORCH_CHECK(x.numel() < (1LL << 31), "x has 2^31 or more elements");
+    TORCH_CHECK(out.numel() < (1LL << 31), "out has 2^31 or more elements");
+    if (res) {
+        check_f32(*res, "res");
+        TORCH_CHECK(res->numel() == out.numel(),
+                    "res must match the output shape");
+    }
+    defer_hip::ConvF32Params p{};
+    p.x = f32ptr(x);
+    p.w = f32ptr(w);
+    p.scale = scale;
+    p.bias = bias;
+    p.res = res ? f32ptr(*res) : nullptr;
+    p.out = out.data_ptr<float>();
+    p.M = (int)M; p.K = R * S * Cin; p.Cout = Cout;
+    p.H = H; p.W = W; p.Cin = Cin;
+    p.OH = OH; p.OW = OW; p.S = S; p.stride = stride; p.pad = pad;
+    p.relu = relu;
+    bool gemm_mode = (R == 1 && S == 1 && stride == 1 && pad == 0);
+    if (M > 0)
+        defer_hip::launch_conv_f32(p, gemm_mode, conv_f32_tile(),
+                                   cur_stream());
+}
+
+Tensor conv2d_bn_act_f32(const Tensor& x, const Tensor& w,
+                         const c10::optional<Tensor>& scale,
+                         const c10::optional<Tensor>& bias,
+                         const c10::optional<Tensor>& res, int64_t stride,
+                         int64_t pad, bool relu) {
+    check_f32(x, "x");
+    check_f32(w, "w");
+    TORCH_CHECK(x.dim() == 4, "x must be NHWC");
+    TORCH_CHECK(w.dim() == 4, "w must be OHWI");
+    TORCH_CHECK(stride >= 1 && pad >= 0, "bad stride/pad");
+    int NB = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3);
+    int Cout = w.size(0), R = w.size(1), S = w.size(2);
+    TORCH_CHECK(w.size(3) == Cin, "w Cin mismatch");
+    TORCH_CHECK(Cout % 4 == 0,
+                "fp32 conv needs Cout % 4 == 0 (16-byte stores), got ",
+                Cout);
+    TORCH_CHECK(H + 2 * pad >= R && W + 2 * pad >= S,
+                "kernel larger than the padded input");
+    int OH = (int)((H + 2 * pad - R) / stride + 1);
+    int OW = (int)((W + 2 * pad - S) / stride + 1);
+    long M = (long)NB * OH * OW;
+    const float* sc = f32_vec_opt(scale, "scale", Cout);
+    const float* bi = f32_vec_opt(bias, "bias", Cout);
+    auto out = at::empty({NB, OH, OW, Cout}, x.options());
+    if (Cin % 4 != 0) {
+        // odd-Cin stems: zero-pad channels to a multiple of 4 (weights
+        // once, cached) so every K chunk is one aligned float4
+        int C4 = (Cin + 3) / 4 * 4;
+        hipStream_t s = cur_stream();
+        auto xp = at::empty({NB, H, W, C4}, x.options());
+        defer_hip::launch_pad_channels_f32(f32ptr(x), xp.data_ptr<float>(),
+                                           (long)NB * H * W, Cin, C4, s);
+        auto wp = cached_weight_prep(w, -4000 - C4, [&] {
+            auto t = at::empty({Cout, R, S, C4}, w.options());
+            defer_hip::launch_pad_channels_f32(
+                f32ptr(w), t.data_ptr<float>(), (long)Cout * R * S, Cin, C4,
+                s);
+            return t;
+        });
+        run_conv_f32(xp, wp, sc, bi, res, out, M, H, W, C4, OH, OW, R, S,
+                     (int)stride, (int)pad, relu);
+        return out;
+    }
+    run_conv_f32(x, w, sc, bi, res, out, M, H, W, Cin, OH, OW, R, S,
+                 (int)stride, (int)pad, relu);
+    return out;
+}
+
+Tensor linear_f32(const Tensor& x, const Tensor& w,
+                  const c10::optional<Tensor>& bias) {
+    check_f32(x, "x");
+    check_f32(w, "w");
+    TORCH_CHECK(x.dim() == 2 && w.dim() == 2, "linear wants 2-D");
+    int M = x.size(0), K = x.size(1), N = w.size(0);
+    TORCH_CHECK(w.size(1) == K, "K mismatch");
+    TORCH_CHECK(K % 4 == 0, "fp32 linear needs K % 4 == 0, got ", K);
+    TORCH_CHECK(N % 4 == 0, "fp32 linear needs N % 4 == 0, got ", N);
+    auto out = at::empty({M, N}, x.options());
+    run_conv_f32(x, w, nullptr, f32_vec_opt(bias, "bias", N), c10::nullopt,
+                 out, M, 1, 1, K, 1, 1, 1, 1, 1, 0, false);
+    return out;
+}
+
 Tensor conv2d_bn_act(Tensor x, Tensor w, c10::optional<Tensor> scale,
                      c10::optional<Tensor> bias, c10::optional<Tensor> res,
                      int64_t stride, int64_t pad, bool relu) {
+    if (is_f32(x, "x"))
+        return conv2d_bn_act_f32(x, w, scale, bias, res, stride, pad, relu);
     check_bf16(x, "x");
     check_bf16(w, "w");
     TORCH_CHECK(x.dim() == 4, "x must be NHWC");
@@ -231,6 +378,7 @@ Tensor conv2d_bn_act(Tensor x, Tensor w, c10::optional<Tensor> scale,
 }
 
 Tensor linear(Tensor x, Tensor w, c10::optional<Tensor> bias) {
+    if (is_f32(x, "x")) return linear_f32(x, w, bias);
     check_bf16(x, "x");
     check_bf16(w, "w");
     TORCH_CHECK(x.dim() == 2 && w.dim() == 2, "linear wants 2-D");
@@ -343,6 +491,21 @@ std::tuple<Tensor, Tensor> conv1x1_chain(
 }
 
 Tensor bn_act(Tensor x, Tensor scale, Tensor bias, bool relu) {
+    if (is_f32(x, "x")) {
+        check_f32(x, "x");
+        int C = x.size(-1);
+        TORCH_CHECK(C % 4 == 0, "fp32 bn_act needs C % 4 == 0, got ", C);
+        TORCH_CHECK(scale.is_cuda() && bias.is_cuda() &&
+                    scale.numel() == C && bias.numel() == C,
+                    "scale/bias must be GPU tensors of length C");
+        auto out = at::empty_like(x);
+        auto sf = scale.to(at::kFloat).contiguous();
+        auto bf = bias.to(at::kFloat).contiguous();
+        defer_hip::launch_bn_act_f32(f32ptr(x), f32ptr(sf), f32ptr(bf),
+                                     out.data_ptr<float>(), x.numel() / 4,
+                                     C / 4, relu, cur_stream());
+        return out;
+    }
     check_bf16(x, "x");
     int C = x.size(-1);
     TORCH_CHECK(C % 8 == 0, "C must be a multiple of 8");
@@ -356,6 +519,18 @@ Tensor bn_act(Tensor x, Tensor scale, Tensor bias, bool relu) {
 }
 
 Tensor add_act(Tensor a, Tensor b, bool relu) {
+    if (is_f32(a, "a")) {
+        check_f32(a, "a");
+        check_f32(b, "b");
+        TORCH_CHECK(a.sizes() == b.sizes(), "shape mismatch");
+        TORCH_CHECK(a.numel() % 4 == 0,
+                    "fp32 add_act needs numel % 4 == 0");
+        auto out = at::empty_like(a);
+        defer_hip::launch_add_act_f32(f32ptr(a), f32ptr(b),
+                                      out.data_ptr<float>(), a.numel() / 4,
+                                      relu, cur_stream());
+        return out;
+    }
     check_bf16(a, "a");
     check_bf16(b, "b");
     TORCH_CHECK(a.sizes() == b.sizes(), "shape mismatch");
@@ -367,6 +542,14 @@ Tensor add_act(Tensor a, Tensor b, bool relu) {
 }
 
 Tensor relu(Tensor x) {
+    if (is_f32(x, "x")) {
+        check_f32(x, "x");
+        TORCH_CHECK(x.numel() % 4 == 0, "fp32 relu needs numel % 4 == 0");
+        auto out = at::empty_like(x);
+        defer_hip::launch_relu_f32(f32ptr(x), out.data_ptr<float>(),
+                                   x.numel() / 4, cur_stream());
+        return out;
+    }
     check_bf16(x, "x");
     TORCH_CHECK(x.numel() % 8 == 0, "numel must be a multiple of 8");
     auto out = at::empty_like(x);
@@ -376,6 +559,16 @@ Tensor relu(Tensor x) {
 }
 
 Tensor softmax(Tensor x) {
+    if (is_f32(x, "x")) {
+        check_f32(x, "x");
+        TORCH_CHECK(x.dim() >= 1 && x.numel() > 0, "softmax of nothing");
+        int cols = x.size(-1);
+        long rows = x.numel() / cols;
+        auto out = at::empty_like(x);
+        defer_hip::launch_softmax_f32(f32ptr(x), out.data_ptr<float>(),
+                                      (int)rows, cols, cur_stream());
+        return out;
+    }
     check_bf16(x, "x");
     int cols = x.size(-1);
     long rows = x.numel() / cols;
@@ -386,6 +579,19 @@ Tensor softmax(Tensor x) {
 }
 
 Tensor maxpool2d(Tensor x, int64_t kernel, int64_t stride, int64_t pad) {
+    if (is_f32(x, "x")) {
+        check_f32(x, "x");
+        TORCH_CHECK(x.dim() == 4, "x must be NHWC");
+        int NB = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+        TORCH_CHECK(C % 4 == 0, "fp32 maxpool2d needs C % 4 == 0, got ", C);
+        int OH = (int)((H + 2 * pad - kernel) / stride + 1);
+        int OW = (int)((W + 2 * pad - kernel) / stride + 1);
+        auto out = at::empty({NB, OH, OW, C}, x.options());
+        defer_hip::launch_maxpool_f32(f32ptr(x), out.data_ptr<float>(), NB, H,
+                                 W, C, OH, OW, (int)kernel, (int)stride,
+                                 (int)pad, cur_stream());
+        return out;
+    }
     check_bf16(x, "x");
     TORCH_CHECK(x.dim() == 4, "x must be NHWC");
     int NB = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
@@ -400,6 +606,19 @@ Tensor maxpool2d(Tensor x, int64_t kernel, int64_t stride, int64_t pad) {
 }
 
 Tensor avgpool2d(Tensor x, int64_t kernel, int64_t stride, int64_t pad) {
+    if (is_f32(x, "x")) {
+        check_f32(x, "x");
+        TORCH_CHECK(x.dim() == 4, "x must be NHWC");
+        int NB = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+        TORCH_CHECK(C % 4 == 0, "fp32 avgpool2d needs C % 4 == 0, got ", C);
+        int OH = (int)((H + 2 * pad - kernel) / stride + 1);
+        int OW = (int)((W + 2 * pad - kernel) / stride + 1);
+        auto out = at::empty({NB, OH, OW, C}, x.options());
+        defer_hip::launch_avgpool_f32(f32ptr(x), out.data_ptr<float>(), NB, H,
+                                 W, C, OH, OW, (int)kernel, (int)stride,
+                                 (int)pad, cur_stream());
+        return out;
+    }
     check_bf16(x, "x");
     TORCH_CHECK(x.dim() == 4, "x must be NHWC");
     int NB = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
@@ -424,8 +643,10 @@ Tensor concat_lastdim(std::vector<Tensor> xs) {
     long rows = 1;
     for (int i = 0; i + 1 < nd; ++i) rows *= base[i];
     long ctot = 0;
+    const bool f32 = is_f32(xs[0], "concat input");
     for (auto& t : xs) {
-        check_bf16(t, "concat input");
+        if (f32) check_f32(t, "concat input");
+        else check_bf16(t, "concat input");
         TORCH_CHECK((int)t.sizes().size() == nd, "rank mismatch");
         for (int i = 0; i + 1 < nd; ++i)
             TORCH_CHECK(t.size(i) == base[i], "leading-dim mismatch");
@@ -434,6 +655,25 @@ Tensor concat_lastdim(std::vector<Tensor> xs) {
     base[nd - 1] = ctot;
     auto out = at::empty(base, xs[0].options());
     hipStream_t s = cur_stream();
+    if (f32) {
+        if (xs.size() == 2 && xs[0].size(nd - 1) % 4 == 0 &&
+            xs[1].size(nd - 1) % 4 == 0) {
+            defer_hip::launch_cat2_f32(f32ptr(xs[0]), f32ptr(xs[1]),
+                                       out.data_ptr<float>(), rows,
+                                       (int)xs[0].size(nd - 1),
+                                       (int)xs[1].size(nd - 1), s);
+            return out;
+        }
+        long coff = 0;
+        for (auto& t : xs) {
+            long cj = t.size(nd - 1);
+            hipMemcpy2DAsync((char*)bptr_mut(out) + coff * 4, ctot * 4,
+                             bptr(t), cj * 4, cj * 4, rows,
+                             hipMemcpyDeviceToDevice, s);
+            coff += cj;
+        }
+        return out;
+    }
     if (xs.size() == 2 && xs[0].size(nd - 1) % 8 == 0 &&
         xs[1].size(nd - 1) % 8 == 0) {
         // the DenseNet shape class: one vectorized kernel beats the
@@ -455,6 +695,18 @@ Tensor concat_lastdim(std::vector<Tensor> xs) {
 }
 
 Tensor global_avg_pool(Tensor x) {
+    if (is_f32(x, "x")) {
+        check_f32(x, "x");
+        TORCH_CHECK(x.dim() == 4, "x must be NHWC");
+        int NB = x.size(0), HW = x.size(1) * x.size(2), C = x.size(3);
+        TORCH_CHECK(C % 4 == 0,
+                    "fp32 global_avg_pool needs C % 4 == 0, got ", C);
+        TORCH_CHECK(HW > 0, "empty spatial extent");
+        auto out = at::empty({NB, C}, x.options());
+        defer_hip::launch_gap_f32(f32ptr(x), out.data_ptr<float>(), NB, HW,
+                                  C, cur_stream());
+        return out;
+    }
     check_bf16(x, "x");
     TORCH_CHECK(x.dim() == 4, "x must be NHWC");
     int NB = x.size(0), HW = x.size(1) * x.size(2), C = x.size(3);

@@ -84,6 +84,50 @@ void launch_avgpool(const void* x, void* y, int NB, int H, int W, int C,
 void launch_gap(const void* x, void* y, int NB, int HW, int C,
                 hipStream_t s);
 
+// ---- fp32 execution path (conv_f32.hip, ops_f32.hip) ----
+// Exact-f32 implicit-GEMM conv on the f32-input MFMA:
+// out = act(conv(x, w) * scale[c] + bias[c] + res). Cin % 4 == 0 and
+// Cout % 4 == 0 (the bindings channel-pad odd-Cin stems); scale, bias
+// and res may each be null (1, 0, none).
+struct ConvF32Params {
+    const float* x;     // [NB, H, W, Cin] (or [M][K] in gemm mode)
+    const float* w;     // [Cout][K] (OHWI flattened)
+    const float* scale; // [Cout] or null
+    const float* bias;  // [Cout] or null
+    const float* res;   // [M][Cout] or null
+    float* out;         // [M][Cout]
+    int M, K, Cout;
+    int H, W, Cin;
+    int OH, OW, S, stride, pad;
+    int relu;
+};
+// tile: 0 = heuristic, 1 = 128x128, 2 = 128x64 (A/B measurement switch)
+void launch_conv_f32(const ConvF32Params& p, bool gemm_mode, int tile,
+                     hipStream_t s);
+void launch_pad_channels_f32(const float* x, float* y, long rows, int C,
+                             int C4, hipStream_t s);
+
+// fp32 elementwise / concat / pooling / softmax: 4 floats per lane where
+// the bf16 kernels take 8 (total4 = numel / 4, c4 = C / 4)
+void launch_bn_act_f32(const float* x, const float* scale, const float* bias,
+                       float* y, long total4, int c4, bool relu,
+                       hipStream_t s);
+void launch_add_act_f32(const float* a, const float* b, float* y,
+                        long total4, bool relu, hipStream_t s);
+void launch_relu_f32(const float* x, float* y, long total4, hipStream_t s);
+void launch_cat2_f32(const float* a, const float* b, float* y, long rows,
+                     int c1, int c2, hipStream_t s);
+void launch_softmax_f32(const float* x, float* y, int rows, int cols,
+                        hipStream_t s);
+void launch_maxpool_f32(const float* x, float* y, int NB, int H, int W,
+                        int C, int OH, int OW, int k, int stride, int pad,
+                        hipStream_t s);
+void launch_avgpool_f32(const float* x, float* y, int NB, int H, int W,
+                        int C, int OH, int OW, int k, int stride, int pad,
+                        hipStream_t s);
+void launch_gap_f32(const float* x, float* y, int NB, int HW, int C,
+                    hipStream_t s);
+
 // fixed-rate ZFP-style codec (see csrc/codec.hip / ops/zfp_ref.py)
 // phases: 3 = full encode; 1/2 run only the transform / serialize phase
 // (perf-bisection harness for tools/codecbench.py --phases)

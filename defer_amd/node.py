@@ -39,6 +39,10 @@ def main():
     ap.add_argument("--compression", default="none",
                     choices=["none", "fp8", "zfp", "zfp+lz4", "auto"])
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"])
+    ap.add_argument("--dtype", default=None, choices=["bf16", "fp32"],
+                    help="compute dtype (default: bf16 on cuda, fp32 on "
+                         "cpu; fp32 on cuda runs the exact-f32 MFMA "
+                         "kernels)")
     ap.add_argument("--dual-rail", action="store_true")
     ap.add_argument("--calibration", default=None,
                     help="per-layer measured-cost file for auto cuts "
@@ -48,6 +52,10 @@ def main():
                     help="per-stage checkpoint dir (checkpoint."
                          "save_stages); cuts come from its manifest")
     args = ap.parse_args()
+    if args.dtype is None:
+        args.dtype = "bf16" if args.device == "cuda" else "fp32"
+    elif args.device == "cpu" and args.dtype != "fp32":
+        ap.error("--device cpu computes in fp32 only")
 
     from defer_amd.config import PipelineConfig
     from defer_amd.models import DEFER_8STAGE_CUTS, MODELS
@@ -75,7 +83,7 @@ def main():
 
     cfg = PipelineConfig(
         partition_layers=cuts, num_stages=world, device=args.device,
-        dtype="bf16" if args.device == "cuda" else "fp32",
+        dtype=args.dtype,
         batch_size=args.batch, use_hip_graphs=False,
         compression=args.compression, dual_rail=args.dual_rail,
         weights_dir=args.weights_dir,
@@ -86,8 +94,7 @@ def main():
     B = args.batch
     model = MODELS[args.model]()
     pipe = DistPipeline(model, cfg, (B, 224, 224, 3), device=dev)
-    dtype = torch.bfloat16 if args.device == "cuda" else torch.float32
-    x = torch.randn(B, 224, 224, 3, device=dev, dtype=dtype)
+    x = torch.randn(B, 224, 224, 3, device=dev, dtype=cfg.torch_dtype())
 
     dist.barrier()   # collective comm init before any p2p op
 

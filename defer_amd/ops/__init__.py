@@ -6,6 +6,13 @@ a CUDA device and the extension is not importable, ops raise — there is no
 silent eager fallback on GPU (the HIP path is the product; the reference's
 equivalent substrate was TensorFlow's native kernels, node.py:106).
 
+GPU tensors may be bf16 (the tuned default) or fp32 (the exact-f32 MFMA
+path, `csrc/conv_f32.hip` + `csrc/ops_f32.hip`); the bindings pick the
+launcher from the tensor's dtype and raise for anything else. The two
+fused 1x1 ops (`conv1x1_prebn`, `conv1x1_chain`) have no fp32 kernel: for
+fp32 GPU tensors they compose the primitive ops of this module, which is
+the same arithmetic the CPU branch runs.
+
 On CPU, ops use the fp32 PyTorch reference implementations (tests and the
 no-GPU plumbing config).
 """
@@ -75,6 +82,12 @@ def conv1x1_prebn(x, w, scale, bias, out_scale=None, out_bias=None):
         if out_scale is not None:
             y = _ref.batchnorm_apply(y, out_scale, out_bias, "relu")
         return y
+    if x.dtype == torch.float32:
+        z = batchnorm_apply(x, scale, bias, "relu")
+        y = conv2d_bn_act(z, w, None, None, 1, 0, "none", None)
+        if out_scale is not None:
+            y = batchnorm_apply(y, out_scale, out_bias, "relu")
+        return y
     return m.conv1x1_prebn(x, w, scale, bias, out_scale, out_bias)
 
 
@@ -104,6 +117,10 @@ def conv1x1_chain(x, w3, s3, b3, residual, act3, w1, s1, b1, act1,
     if m is None:
         y = _ref.conv2d_bn_act(x, w3, s3, b3, 1, 0, act3, residual)
         a2 = _ref.conv2d_bn_act(y, w1, s1, b1, 1, 0, act1, None)
+        return y, a2
+    if x.dtype == torch.float32:
+        y = conv2d_bn_act(x, w3, s3, b3, 1, 0, act3, residual)
+        a2 = conv2d_bn_act(y, w1, s1, b1, 1, 0, act1, None)
         return y, a2
     return m.conv1x1_chain(x, w3, s3, b3, residual, act3 == "relu", w1, s1,
                            b1, act1 == "relu",

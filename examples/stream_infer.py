@@ -33,6 +33,9 @@ def main():
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--cuts", default="auto",
                     help='"auto", "defer8", or comma-separated names')
+    ap.add_argument("--dtype", default=None, choices=["bf16", "fp32"],
+                    help="compute dtype (default: bf16 on cuda, fp32 on "
+                         "cpu)")
     args = ap.parse_args()
 
     model = MODELS[args.model]()
@@ -41,11 +44,14 @@ def main():
             else [c for c in args.cuts.split(",") if c])
 
     on_gpu = args.device.startswith("cuda")
+    if args.dtype is None:
+        args.dtype = "bf16" if on_gpu else "fp32"
+    elif not on_gpu and args.dtype != "fp32":
+        ap.error("--device cpu computes in fp32 only")
     engine = DEFER([args.device] * args.nodes,
                    config=PipelineConfig(device="cuda" if on_gpu
                                          else "cpu",
-                                         dtype="bf16" if on_gpu
-                                         else "fp32"))
+                                         dtype=args.dtype))
     if cuts is not None and len(cuts) + 1 != args.nodes:
         raise SystemExit(f"{len(cuts)} cuts make {len(cuts) + 1} stages "
                          f"but --nodes is {args.nodes}")
@@ -63,7 +69,7 @@ def main():
     t = threading.Thread(target=serve)
     t.start()
 
-    dtype = torch.bfloat16 if on_gpu else torch.float32
+    dtype = engine.cfg.torch_dtype()
     x = torch.randn(args.batch, 224, 224, 3, dtype=dtype,
                     device=args.device if on_gpu else "cpu")
     t0 = time.perf_counter()

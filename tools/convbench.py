@@ -3,6 +3,8 @@
 
 Times every distinct ResNet50/VGG19 conv shape at the bench batch size and
 prints us/call, TFLOP/s and achieved GB/s next to a roofline estimate.
+`--dtype fp32` times the exact-f32 MFMA conv (csrc/conv_f32.hip); its
+ceiling is the 157 TF f32 matrix peak, one sixteenth of bf16.
 """
 
 import argparse
@@ -49,16 +51,18 @@ VGG_SHAPES = [
 ]
 
 
-def bench_shape(name, H, W, Cin, Cout, R, stride, pad, res, B, iters=30):
+def bench_shape(name, H, W, Cin, Cout, R, stride, pad, res, B, iters=30,
+                dtype=torch.bfloat16, warmup=5):
     dev = "cuda:0"
-    x = torch.randn(B, H, W, Cin, device=dev, dtype=torch.bfloat16)
-    w = torch.randn(Cout, R, R, Cin, device=dev, dtype=torch.bfloat16) * 0.05
+    esz = 2 if dtype == torch.bfloat16 else 4
+    x = torch.randn(B, H, W, Cin, device=dev, dtype=dtype)
+    w = torch.randn(Cout, R, R, Cin, device=dev, dtype=dtype) * 0.05
     sc = torch.rand(Cout, device=dev) + 0.5
     bi = torch.randn(Cout, device=dev) * 0.1
     OH = (H + 2 * pad - R) // stride + 1
-    rt = (torch.randn(B, OH, OH, Cout, device=dev, dtype=torch.bfloat16)
+    rt = (torch.randn(B, OH, OH, Cout, device=dev, dtype=dtype)
           if res else None)
-    for _ in range(5):
+    for _ in range(warmup):
         y = ops.conv2d_bn_act(x, w, sc, bi, stride=stride, padding=pad,
                               act="relu", residual=rt)
     torch.cuda.synchronize()
@@ -76,8 +80,8 @@ def bench_shape(name, H, W, Cin, Cout, R, stride, pad, res, B, iters=30):
     fl = 2.0 * M * Cout * K
     tf = fl / us / 1e6
     # min traffic: x once, out once, weights once (tiny)
-    gb = (x.numel() * 2 + y.numel() * 2 + w.numel() * 2
-          + (rt.numel() * 2 if res else 0)) / us / 1e3
+    gb = (x.numel() * esz + y.numel() * esz + w.numel() * esz
+          + (rt.numel() * esz if res else 0)) / us / 1e3
     return dict(name=name, us=round(us, 1), tflops=round(tf, 1),
                 min_gbps=round(gb, 0), M=M, K=K, N=Cout)
 
@@ -87,12 +91,15 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--model", default="resnet50")
     ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     args = ap.parse_args()
+    dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     shapes = RESNET_SHAPES if args.model == "resnet50" else VGG_SHAPES
     total = 0.0
     rows = []
     for s in shapes:
-        r = bench_shape(*s, args.batch, args.iters)
+        r = bench_shape(*s, args.batch, args.iters, dtype, args.warmup)
         rows.append(r)
         print(f"{r['name']:22s} M={r['M']:7d} N={r['N']:4d} K={r['K']:5d} "
               f"{r['us']:8.1f} us  {r['tflops']:7.1f} TF  "
