@@ -605,6 +605,94 @@ Tensor maxpool2d(Tensor x, int64_t kernel, int64_t stride, int64_t pad) {
     return out;
 }
 
+// What the fused stem path did, for tests: how many times the kernel was
+// launched in this process and the band split of the last launch.
+struct StemPoolStats {
+    std::mutex mu;
+    int64_t launches = 0;
+    int64_t bands = 0, rows_per_band = 0;
+};
+StemPoolStats& stem_pool_stats_ref() {
+    static StemPoolStats st;
+    return st;
+}
+
+py::dict stem_pool_stats() {
+    auto& st = stem_pool_stats_ref();
+    std::lock_guard<std::mutex> g(st.mu);
+    py::dict d;
+    d["launches"] = st.launches;
+    d["bands"] = st.bands;
+    d["rows_per_band"] = st.rows_per_band;
+    return d;
+}
+
+Tensor conv_bn_act_maxpool(Tensor x, Tensor w, c10::optional<Tensor> scale,
+                           c10::optional<Tensor> bias, int64_t stride,
+                           int64_t pad, bool relu, int64_t pool_kernel,
+                           int64_t pool_stride, int64_t pool_pad,
+                           int64_t mode, int64_t max_blocks) {
+    // maxpool(act(conv(x, w)*scale + bias)). mode 0: fused kernel where
+    // the policy says so; 1: fused wherever the kernel covers the shape;
+    // 2: always two launches. bf16 only (ops composes the fp32 path).
+    check_bf16(x, "x");
+    check_bf16(w, "w");
+    TORCH_CHECK(x.dim() == 4, "x must be NHWC");
+    TORCH_CHECK(w.dim() == 4, "w must be OHWI");
+    TORCH_CHECK(mode >= 0 && mode <= 2, "mode must be 0, 1 or 2");
+    TORCH_CHECK(max_blocks >= 0, "max_blocks must be >= 0");
+    int NB = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3);
+    int Cout = w.size(0), R = w.size(1), S = w.size(2);
+    TORCH_CHECK(w.size(3) == Cin, "w Cin mismatch");
+    TORCH_CHECK((!scale || scale->numel() == Cout) &&
+                (!bias || bias->numel() == Cout),
+                "scale/bias length must equal Cout");
+    int OH = (int)((H + 2 * pad - R) / stride + 1);
+    int OW = (int)((W + 2 * pad - S) / stride + 1);
+    // policy: the fused kernel won the A/B at batch 256, 64, 8 and 1
+    // (docs/OPTIMIZATION_LOG.md), so mode 0 takes it wherever it is legal
+    // and is the same as mode 1 today
+    if (mode != 2 && NB > 0 && OH > 0 && OW > 0 &&
+        (long)NB * OH * OW < (1LL << 31) &&
+        defer_hip::stem_pool_supported(Cin, Cout, R, S, (int)stride,
+                                       (int)pad, relu, (int)pool_kernel,
+                                       (int)pool_stride, (int)pool_pad,
+                                       OH, OW)) {
+        hipStream_t s = cur_stream();
+        // same repacked weights as the STEM path of conv2d_bn_act
+        // (TR = 24, K = 168); the kernel pads the raw input itself
+        const int TR = 24, Keff = R * TR;
+        auto wp = cached_weight_prep(w, TR, [&] {
+            auto t = at::empty({Cout, Keff}, w.options());
+            defer_hip::launch_stem_repack_w(bptr(w), bptr_mut(t), Cout, R,
+                                            S, Cin, TR, s);
+            return t;
+        });
+        int POH = (OH + 2 - 3) / 2 + 1, POW = (OW + 2 - 3) / 2 + 1;
+        auto out = at::empty({NB, POH, POW, Cout}, x.options());
+        defer_hip::StemPoolParams q{};
+        q.x = bptr(x);
+        q.wp = bptr(wp);
+        q.scale = fptr_opt(scale, "scale", ones_buf(), Cout);
+        q.bias = fptr_opt(bias, "bias", zeros_buf(), Cout);
+        q.out = bptr_mut(out);
+        q.NB = NB; q.H = H; q.W = W;
+        q.OH = OH; q.OW = OW; q.POH = POH; q.POW = POW;
+        auto used = defer_hip::launch_stem_pool(q, (int)max_blocks, s);
+        {
+            auto& st = stem_pool_stats_ref();
+            std::lock_guard<std::mutex> g(st.mu);
+            ++st.launches;
+            st.bands = used.bands;
+            st.rows_per_band = used.rpb;
+        }
+        return out;
+    }
+    auto y = conv2d_bn_act(x, w, scale, bias, c10::nullopt, stride, pad,
+                           relu);
+    return maxpool2d(y, pool_kernel, pool_stride, pool_pad);
+}
+
 Tensor avgpool2d(Tensor x, int64_t kernel, int64_t stride, int64_t pad) {
     if (is_f32(x, "x")) {
         check_f32(x, "x");
@@ -856,6 +944,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("s3"), py::arg("b3"), py::arg("res"), py::arg("relu3"),
           py::arg("w1"), py::arg("s1"), py::arg("b1"), py::arg("relu1"),
           py::arg("mode") = 0, py::arg("max_blocks") = 0);
+    m.def("conv_bn_act_maxpool", &conv_bn_act_maxpool, py::arg("x"),
+          py::arg("w"), py::arg("scale"), py::arg("bias"),
+          py::arg("stride"), py::arg("pad"), py::arg("relu"),
+          py::arg("pool_kernel"), py::arg("pool_stride"),
+          py::arg("pool_pad"), py::arg("mode") = 0,
+          py::arg("max_blocks") = 0);
+    m.def("stem_pool_stats", &stem_pool_stats);
     m.def("add_act", &add_act);
     m.def("relu", &relu);
     m.def("softmax", &softmax);

@@ -65,6 +65,31 @@ bool launch_conv1x1_chain(const void* x, const void* w3, const float* s3,
                           int K1, int N1, int N2, bool force,
                           int max_blocks, hipStream_t s);
 
+// fused stem (stem_pool.hip): 7x7/s2/p3 Cin=3 Cout=64 conv + folded BN +
+// ReLU + 3x3/s2/p1 max-pool, writing only the pooled tensor; bit-identical
+// to launch_pad2d + the STEM launch_conv_igemm + launch_maxpool. x is the
+// raw input (the zero padding is folded into the kernel's staging) and wp
+// the launch_stem_repack_w weights (TR = 24).
+struct StemPoolParams {
+    const void* x;      // [NB, H, W, 3] bf16
+    const void* wp;     // [64][168] bf16
+    const float* scale; // [64]
+    const float* bias;  // [64]
+    void* out;          // [NB, POH, POW, 64] bf16
+    int NB, H, W;       // input dims
+    int OH, OW;         // conv output dims
+    int POH, POW;       // pooled output dims
+    int bands, rpb;     // filled by the launcher: bands/image, rows/band
+};
+// true when the fused kernel covers this conv + pool class and width
+bool stem_pool_supported(int Cin, int Cout, int R, int S, int stride,
+                         int pad, bool relu, int pk, int ps, int pp,
+                         int OH, int OW);
+// max_blocks caps the grid (0 = policy) so a few blocks walk many bands.
+// Returns the parameters it launched with (bands and rpb filled in).
+StemPoolParams launch_stem_pool(const StemPoolParams& p, int max_blocks,
+                                hipStream_t s);
+
 void launch_bn_act(const void* x, const float* scale, const float* bias,
                    void* y, long total8, int c8, bool relu, hipStream_t s);
 void launch_add_act(const void* a, const void* b, void* y, long total8,

@@ -8,10 +8,10 @@ equivalent substrate was TensorFlow's native kernels, node.py:106).
 
 GPU tensors may be bf16 (the tuned default) or fp32 (the exact-f32 MFMA
 path, `csrc/conv_f32.hip` + `csrc/ops_f32.hip`); the bindings pick the
-launcher from the tensor's dtype and raise for anything else. The two
-fused 1x1 ops (`conv1x1_prebn`, `conv1x1_chain`) have no fp32 kernel: for
-fp32 GPU tensors they compose the primitive ops of this module, which is
-the same arithmetic the CPU branch runs.
+launcher from the tensor's dtype and raise for anything else. The fused
+ops (`conv1x1_prebn`, `conv1x1_chain`, `conv_bn_act_maxpool`) have no fp32
+kernel: for fp32 GPU tensors they compose the primitive ops of this module,
+which is the same arithmetic the CPU branch runs.
 
 On CPU, ops use the fp32 PyTorch reference implementations (tests and the
 no-GPU plumbing config).
@@ -125,6 +125,54 @@ def conv1x1_chain(x, w3, s3, b3, residual, act3, w1, s1, b1, act1,
     return m.conv1x1_chain(x, w3, s3, b3, residual, act3 == "relu", w1, s1,
                            b1, act1 == "relu",
                            _CHAIN_MODE if mode is None else mode, max_blocks)
+
+
+# A/B switch for the fused stem conv + max-pool kernel (same convention as
+# DEFER_CONV_CHAIN): unset = the binding's policy, "0" = always two
+# launches, "force" = fused wherever the kernel covers the shape.
+_STEM_POOL_MODES = {None: 0, "": 0, "force": 1, "0": 2}
+_stem_pool_env = os.environ.get("DEFER_STEM_POOL")
+if _stem_pool_env not in _STEM_POOL_MODES:
+    raise ValueError(
+        f"DEFER_STEM_POOL={_stem_pool_env!r}: expected unset, '0' or 'force'")
+_STEM_POOL_MODE = _STEM_POOL_MODES[_stem_pool_env]
+
+
+def conv_bn_act_maxpool(x, w, scale, bias, stride, padding, act,
+                        pool_kernel, pool_stride, pool_padding, mode=None,
+                        max_blocks=0):
+    """maxpool2d(conv2d_bn_act(x, w, scale, bias, act=act)) in one call,
+    identical to the two ops it replaces. On GPU the 7x7/s2 Cin=3 Cout=64
+    ReLU stem followed by a 3x3/s2/p1 pool runs as one kernel
+    (csrc/stem_pool.hip) that never writes the conv activation; every other
+    geometry runs the two launches. mode: 0 = policy, 1 = fused wherever
+    legal, 2 = two launches; None = DEFER_STEM_POOL."""
+    m = _backend(x)
+    if m is None:
+        y = _ref.conv2d_bn_act(x, w, scale, bias, stride, padding, act, None)
+        return _ref.maxpool2d(y, pool_kernel, pool_stride, pool_padding)
+    if x.dtype == torch.float32:
+        y = conv2d_bn_act(x, w, scale, bias, stride, padding, act, None)
+        return maxpool2d(y, pool_kernel, pool_stride, pool_padding)
+    if act not in ("relu", "none"):
+        raise ValueError(f"act={act!r}: expected 'relu' or 'none'")
+    return m.conv_bn_act_maxpool(x, w, scale, bias, stride, padding,
+                                 act == "relu", pool_kernel, pool_stride,
+                                 pool_padding,
+                                 _STEM_POOL_MODE if mode is None else mode,
+                                 max_blocks)
+
+
+def stem_pool_stats():
+    """What the fused stem path of conv_bn_act_maxpool did in this process:
+    {"launches": fused-kernel launches so far, "bands", "rows_per_band":
+    the band split of the last one}. Lets tests tell the fused kernel from
+    the two launches, whose results are identical by design."""
+    m = _load_hip()
+    if m is None:
+        raise RuntimeError(
+            f"defer_amd HIP extension is not built: {_hip_err!r}")
+    return dict(m.stem_pool_stats())
 
 
 def batchnorm_apply(x, scale, bias, act="none"):

@@ -14,9 +14,16 @@ block's 1x1 conv1 (ops.conv1x1_chain): add_k is the widest tensor of the
 block and conv1 reads it straight back, so one kernel computes both and
 add_k is never re-read.
 
+A third pass, fuse_conv_pool, merges a conv whose only consumer is a
+max-pool into one node (ops.conv_bn_act_maxpool): for the 7x7/s2 stem of
+the ResNets and DenseNet121 the HIP kernel then writes only the pooled
+tensor, a quarter of the conv activation it would otherwise write and
+read back.
+
 Cut-point names are preserved: the fused node takes the AddAct node's
-name, so partition boundaries at `add_N` (test/test.py:18) still resolve.
-Fusion happens per stage AFTER partitioning.
+(for fuse_conv_pool: the pool's) name, so partition boundaries at `add_N`
+(test/test.py:18) and `pool1` still resolve. Fusion happens per stage
+AFTER partitioning.
 """
 
 from typing import List
@@ -24,7 +31,7 @@ from typing import List
 import torch.nn as nn
 
 from defer_amd.graph import GraphNode, LayerGraph
-from defer_amd.models.layers import AddAct, ConvBNAct
+from defer_amd.models.layers import AddAct, ConvBNAct, MaxPool
 
 
 class FusedConvAddAct(nn.Module):
@@ -157,4 +164,67 @@ def fuse_expand_reduce(graph: LayerGraph) -> LayerGraph:
                                list(n.inputs), dict(n.kwargs)))
         nodes.append(GraphNode(n.name, _Pick(0), [pair]))
         nodes.append(GraphNode(c.name, _Pick(1), [pair]))
+    return LayerGraph(nodes, output=graph.output)
+
+
+class FusedConvPool(nn.Module):
+    """pool(conv(x)) in one call. Both original modules stay referenced
+    (not copied), so parameters are shared with the unfused graph."""
+
+    def __init__(self, conv: ConvBNAct, pool: MaxPool):
+        super().__init__()
+        self.conv = conv
+        self.pool = pool
+
+    def forward(self, x):
+        from defer_amd import ops
+
+        c, q = self.conv, self.pool
+        return ops.conv_bn_act_maxpool(
+            x, c.weight.to(x.dtype), c.scale, c.bias, c.stride, c.padding,
+            c.act, q.kernel, q.stride, q.padding)
+
+
+def _is_stem_pool(c: ConvBNAct, q: MaxPool) -> bool:
+    return (c.cin == 3 and c.cout == 64 and c.kernel == 7 and c.stride == 2
+            and c.padding == 3 and c.act == "relu"
+            and (q.kernel, q.stride, q.padding) == (3, 2, 1))
+
+
+def fuse_conv_pool(graph: LayerGraph) -> LayerGraph:
+    """Rewrite ConvBNAct -> MaxPool pairs into one FusedConvPool node that
+    takes the pool's name. The conv must feed the pool and nothing else,
+    take no residual and not be the graph output; a pool in another stage
+    is simply not matched. Only the geometry the fused kernel serves is
+    rewritten (_is_stem_pool); VGG's 3x3 conv -> 2x2/p0 pool pairs would
+    run the op's two launches anyway and are left as they are."""
+    consumers = {}
+    for n in graph.nodes:
+        for p in n.inputs:
+            consumers.setdefault(p, []).append(n)
+
+    partner = {}                       # conv name -> pool node
+    for n in graph.nodes:
+        if not (type(n.layer) is ConvBNAct and len(n.inputs) == 1
+                and not n.kwargs and n.name != graph.output):
+            continue
+        cs = consumers.get(n.name, [])
+        if (len(cs) == 1 and type(cs[0].layer) is MaxPool
+                and cs[0].inputs == [n.name] and not cs[0].kwargs
+                and _is_stem_pool(n.layer, cs[0].layer)):
+            partner[n.name] = cs[0]
+    pools = {q.name: c for c, q in partner.items()}
+
+    by_name = {n.name: n for n in graph.nodes}
+    nodes: List[GraphNode] = []
+    for n in graph.nodes:
+        if n.name in partner:
+            continue                   # folded into its pool's node
+        c = pools.get(n.name)
+        if c is None:
+            nodes.append(n)
+            continue
+        conv = by_name[c]
+        nodes.append(GraphNode(n.name, FusedConvPool(conv.layer, n.layer),
+                               list(conv.inputs)))
     return LayerGraph(nodes, output=graph.output)
