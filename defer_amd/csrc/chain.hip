@@ -24,13 +24,17 @@
 //   - after the last chunk acc2 gets s1/b1/act1, is bounced as bf16 and
 //     stored with 16-B stores.
 // LDS: (K1 + K1 + N2) * 128 B + 16 KiB = 40..80 KiB -> 2-3 blocks/CU
-// for the layer1/layer2 shape classes, 112..144 KiB (one block) for the
-// layer3 ones.
+// of four waves for the layer1/layer2 shape classes. The layer3 classes
+// (K1 = 256: 120 / 152 KiB, one block per CU) run the same phases with
+// EIGHT waves, so that every SIMD still holds two (NW = 8, "DEEP" below):
+// GEMM1 and GEMM2 split 2 x 4 over the waves, epilogue 1 is one 64-row
+// round that all eight waves write (16 KiB bounce), and the barrier
+// after GEMM1 is folded into the bounce's own, three per chunk.
 //
 // Loads are issued ahead of their use: the residual chunk RES(j+1) — the
 // HBM-bound stream — right after the W1(j) stage, a whole chunk early
 // (epilogue 1 waits vmcnt(2), so exactly those two loads stay in
-// flight); W1(j) before GEMM1(j); W3(j+1) before GEMM2(j); the next A
+// flight; one load and vmcnt(1) with eight waves); W1(j) before GEMM1(j); W3(j+1) before GEMM2(j); the next A
 // panel under the a2 store phase. Every global_load_lds sits after the
 // last LDS write of its phase: the compiler drains pending LDS DMA in
 // front of LDS stores. Co-resident blocks cover the rest.
@@ -44,8 +48,6 @@
 #include "kernels.h"
 
 #define CH_BM 64
-#define CH_TPB 256
-#define CH_SCR (32 * 64 * 2)        // fp32 bounce, 32 rows, in bf16 units
 #define CH_YT (64 * 64)             // y-tile, bf16 units
 
 __device__ __forceinline__ int ch_swz(int row, int k8) {
@@ -59,8 +61,8 @@ __device__ __forceinline__ void ch_glds16(const bf16* src, bf16* lds_base) {
         16, 0, 0);
 }
 
-template <int K1, int N2, int WPS>
-__global__ __launch_bounds__(CH_TPB, WPS) void conv1x1_chain_kernel(
+template <int K1, int N2, int NW, int WPS>
+__global__ __launch_bounds__(NW * WAVE, WPS) void conv1x1_chain_kernel(
     const bf16* __restrict__ X,      // [M][K1]
     const bf16* __restrict__ W3,     // [N1][K1]
     const float* __restrict__ S3,    // [N1]
@@ -72,71 +74,82 @@ __global__ __launch_bounds__(CH_TPB, WPS) void conv1x1_chain_kernel(
     const float* __restrict__ B1,    // [N2]
     bf16* __restrict__ A2,           // [M][N2]
     int M, int N1, int act3, int act1) {
+    constexpr int TPB = NW * WAVE;
+    constexpr bool DEEP = NW == 8;           // two waves per SIMD, one block
+    constexpr int WNS = NW / 2;              // waves across n (2 row slabs)
+    constexpr int WN1 = 64 / WNS;            // GEMM1 wave n-width
+    constexpr int NI1 = WN1 / 16;
     constexpr int NK1 = K1 / 64;             // k-tiles of GEMM1
     constexpr int NT2 = N2 / 64;             // 64-row tiles of the W1 slice
-    constexpr int WN2 = N2 / 2;              // GEMM2 wave n-width
+    constexpr int WN2 = N2 / WNS;            // GEMM2 wave n-width
     constexpr int NI2 = WN2 / 16;
     constexpr int OST = N2 + 8;              // bf16 out-bounce row stride
+    constexpr int CPT = 512 / TPB;           // 16-B chunks of a tile/thread
+    constexpr int ER = TPB / 8;              // rows per epilogue-1 round
+    constexpr int NR = CH_BM / ER;           // epilogue-1 rounds
+    constexpr int SCR = ER * 64 * 2;         // fp32 bounce, in bf16 units
+    static_assert(NW == 4 || NW == 8, "2 x 2 or 2 x 4 waves");
+    static_assert(CH_BM * OST <= N2 * 64 + SCR + CH_YT, "out-bounce fits");
 
     __shared__ __attribute__((aligned(16)))
-    bf16 lds[CH_BM * K1 + 64 * K1 + N2 * 64 + CH_SCR + CH_YT];
+    bf16 lds[CH_BM * K1 + 64 * K1 + N2 * 64 + SCR + CH_YT];
     bf16* Ap = lds;                          // NK1 tiles [64][64]
     bf16* W3b = Ap + CH_BM * K1;             // NK1 tiles [64 n][64 k]
     bf16* W1b = W3b + 64 * K1;               // [N2][64]
     float* scratch = (float*)(W1b + N2 * 64);
-    bf16* ytile = W1b + N2 * 64 + CH_SCR;
+    bf16* ytile = W1b + N2 * 64 + SCR;
     bf16* obuf = W1b;                        // epilogue 2: W1b..ytile end
 
     const int tid = threadIdx.x;
     const int wave = tid / WAVE;
     const int lane = tid % WAVE;
-    const int wm = wave >> 1;                // 32-row slab
-    const int wn = wave & 1;
+    const int wm = wave / WNS;               // 32-row slab
+    const int wn = wave % WNS;
     const int lo16 = lane & 15;
     const int hi4 = lane >> 4;
     const int mtiles = (M + CH_BM - 1) / CH_BM;
     const int NJ = N1 / 64;
 
-    // staging geometry of one [64][64] tile: 2 chunks of 16 B per thread
-    int t_row[2], t_k8[2];
+    // staging geometry of one [64][64] tile: CPT chunks of 16 B per thread
+    int t_row[CPT], t_k8[CPT];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        int chunk = wave * 128 + i * 64 + lane;
+    for (int i = 0; i < CPT; ++i) {
+        int chunk = wave * (64 * CPT) + i * 64 + lane;
         t_row[i] = chunk / 8;
         t_k8[i] = ch_swz(t_row[i], chunk % 8);
     }
     auto stage_a = [&](int mt) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
+        for (int i = 0; i < CPT; ++i) {
             int m = mt * CH_BM + t_row[i];
             if (m >= M) m = M - 1;           // clamped rows are never stored
             const bf16* src = X + (long)m * K1 + t_k8[i] * 8;
 #pragma unroll
             for (int kt = 0; kt < NK1; ++kt)
                 ch_glds16(src + kt * 64,
-                          Ap + kt * 4096 + (wave * 128 + i * 64) * 8);
+                          Ap + kt * 4096 + (wave * (64 * CPT) + i * 64) * 8);
         }
     };
     auto stage_w3 = [&](int j) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
+        for (int i = 0; i < CPT; ++i) {
             const bf16* src =
                 W3 + (long)(j * 64 + t_row[i]) * K1 + t_k8[i] * 8;
 #pragma unroll
             for (int kt = 0; kt < NK1; ++kt)
                 ch_glds16(src + kt * 64,
-                          W3b + kt * 4096 + (wave * 128 + i * 64) * 8);
+                          W3b + kt * 4096 + (wave * (64 * CPT) + i * 64) * 8);
         }
     };
     auto stage_w1 = [&](int j) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
+        for (int i = 0; i < CPT; ++i) {
             const bf16* src =
                 W1 + (long)t_row[i] * N1 + j * 64 + t_k8[i] * 8;
 #pragma unroll
             for (int t = 0; t < NT2; ++t)
                 ch_glds16(src + (long)t * 64 * N1,
-                          W1b + t * 4096 + (wave * 128 + i * 64) * 8);
+                          W1b + t * 4096 + (wave * (64 * CPT) + i * 64) * 8);
         }
     };
 
@@ -149,7 +162,7 @@ __global__ __launch_bounds__(CH_TPB, WPS) void conv1x1_chain_kernel(
     }
 
     // epilogue-1 chunk geometry: one 8-column chunk per thread per round
-    const int e_rl = tid >> 3;               // round-local row 0..31
+    const int e_rl = tid >> 3;               // round-local row 0..ER-1
     const int e_c8 = (tid & 7) * 8;
     const int e_cs = e_c8 ^ (((e_rl >> 2) & 3) << 4);
 
@@ -157,25 +170,25 @@ __global__ __launch_bounds__(CH_TPB, WPS) void conv1x1_chain_kernel(
     if (mt >= mtiles) return;
     stage_a(mt);
     stage_w3(0);
-    float sc3n[2], bi3n[2];
+    float sc3n[NI1], bi3n[NI1];
 #pragma unroll
-    for (int ni = 0; ni < 2; ++ni) {
-        int n = wn * 32 + ni * 16 + lo16;
+    for (int ni = 0; ni < NI1; ++ni) {
+        int n = wn * WN1 + ni * 16 + lo16;
         sc3n[ni] = S3[n];
         bi3n[ni] = B3[n];
     }
 
-    // residual chunk (rows m0.., columns j*64..) of this thread's two
+    // residual chunk (rows m0.., columns j*64..) of this thread's
     // epilogue-1 rounds; rows past M are clamped and never stored
     auto res_load = [&](bf16x8* rv, int m0, int j) {
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            int m = m0 + h * 32 + e_rl;
+        for (int h = 0; h < NR; ++h) {
+            int m = m0 + h * ER + e_rl;
             if (m >= M) m = M - 1;
             rv[h] = load_bf16x8(RES + (long)m * N1 + j * 64 + e_c8);
         }
     };
-    bf16x8 rvn[2];
+    bf16x8 rvn[NR];
     res_load(rvn, mt * CH_BM, 0);
 
     for (; mt < mtiles; mt += gridDim.x) {
@@ -196,37 +209,59 @@ __global__ __launch_bounds__(CH_TPB, WPS) void conv1x1_chain_kernel(
             const int jn = j + 1 < NJ ? j + 1 : 0;
             // s3/b3 and the residual run one chunk ahead (wrapping to
             // chunk 0 of the next tile): the residual is the HBM stream,
-            // and a whole chunk of work covers its latency
-            float sc3[2], bi3[2];
+            // and a whole chunk of work covers its latency.
+            // DEEP hands them over with a move it places itself, here,
+            // where the wait above has covered their loads. The compiler
+            // places its copy at the end of the chunk and, unable to count
+            // across the back edge, waits there for vmcnt(0): the W3 stage
+            // and the residual load would drain in the middle of GEMM2
+            bf16x8 rv[NR];
 #pragma unroll
-            for (int ni = 0; ni < 2; ++ni) {
-                sc3[ni] = sc3n[ni];
-                bi3[ni] = bi3n[ni];
-                int n = jn * 64 + wn * 32 + ni * 16 + lo16;
+            for (int h = 0; h < NR; ++h) {
+                if constexpr (DEEP) {
+                    u32x4 t = __builtin_bit_cast(u32x4, rvn[h]), c;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        asm volatile("v_mov_b32 %0, %1"
+                                     : "=v"(c[q]) : "v"(t[q]) : "memory");
+                    rv[h] = __builtin_bit_cast(bf16x8, c);
+                } else {
+                    rv[h] = rvn[h];
+                }
+            }
+            float sc3[NI1], bi3[NI1];
+#pragma unroll
+            for (int ni = 0; ni < NI1; ++ni) {
+                if constexpr (DEEP) {
+                    asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3"
+                                 : "=&v"(sc3[ni]), "=&v"(bi3[ni])
+                                 : "v"(sc3n[ni]), "v"(bi3n[ni]) : "memory");
+                } else {
+                    sc3[ni] = sc3n[ni];
+                    bi3[ni] = bi3n[ni];
+                }
+                int n = jn * 64 + wn * WN1 + ni * 16 + lo16;
                 sc3n[ni] = S3[n];
                 bi3n[ni] = B3[n];
             }
-            bf16x8 rv[2];
-            rv[0] = rvn[0];
-            rv[1] = rvn[1];
             stage_w1(j);
-            // exactly two loads, unconditionally, AFTER the W1 stage: the
+            // exactly NR loads, unconditionally, AFTER the W1 stage: the
             // counted wait in front of epilogue 1 lets them stay in flight
             res_load(rvn, (j + 1 < NJ || !more) ? m0 : m0 + (int)gridDim.x
                                                           * CH_BM, jn);
 
             // ---- GEMM1: acc1[64x64] = Apanel @ W3_j^T (igemm mapping)
-            f32x4 acc1[2][2];
+            f32x4 acc1[2][NI1];
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-                for (int ni = 0; ni < 2; ++ni)
+                for (int ni = 0; ni < NI1; ++ni)
                     acc1[mi][ni] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kt = 0; kt < NK1; ++kt)
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
-                    bf16x8 af[2], bfr[2];
+                    bf16x8 af[2], bfr[NI1];
 #pragma unroll
                     for (int mi = 0; mi < 2; ++mi) {
                         int row = wm * 32 + mi * 16 + lo16;
@@ -235,8 +270,8 @@ __global__ __launch_bounds__(CH_TPB, WPS) void conv1x1_chain_kernel(
                                + ch_swz(row, ks * 4 + hi4) * 8);
                     }
 #pragma unroll
-                    for (int ni = 0; ni < 2; ++ni) {
-                        int row = wn * 32 + ni * 16 + lo16;
+                    for (int ni = 0; ni < NI1; ++ni) {
+                        int row = wn * WN1 + ni * 16 + lo16;
                         bfr[ni] = *reinterpret_cast<bf16x8*>(
                             W3b + kt * 4096 + row * 64
                                 + ch_swz(row, ks * 4 + hi4) * 8);
@@ -244,28 +279,34 @@ __global__ __launch_bounds__(CH_TPB, WPS) void conv1x1_chain_kernel(
 #pragma unroll
                     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-                        for (int ni = 0; ni < 2; ++ni)
+                        for (int ni = 0; ni < NI1; ++ni)
                             acc1[mi][ni] = MFMA_BF16_16x16x32(
                                 af[mi], bfr[ni], acc1[mi][ni]);
                 }
-            // W1(j) landed; only the two residual loads for the next
+            // W1(j) landed; only the NR residual loads for the next
             // chunk, issued after it, may stay in flight. A panel and W3b
-            // are free after the barrier
-            asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
+            // are free after the barrier; DEEP has nothing to free here
+            // (W3b is restaged two barriers later) and lets the bounce's
+            // own barrier publish W1(j)
+            if constexpr (NR == 2)
+                asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
+            else
+                asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
+            if constexpr (!DEEP) __builtin_amdgcn_s_barrier();
 
-            // ---- epilogue 1: two 32-row rounds through the fp32 bounce
+            // ---- epilogue 1: NR rounds of ER rows through the fp32
+            // bounce; the waves whose slab lies in the round write it
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                if (wm == h) {
+            for (int h = 0; h < NR; ++h) {
+                if (NR == 1 || wm * 32 / ER == h) {
 #pragma unroll
                     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-                        for (int ni = 0; ni < 2; ++ni)
+                        for (int ni = 0; ni < NI1; ++ni)
 #pragma unroll
                             for (int e = 0; e < 4; ++e) {
-                                int rl = mi * 16 + hi4 * 4 + e;
-                                int c = wn * 32 + ni * 16 + lo16;
+                                int rl = wm * 32 % ER + mi * 16 + hi4 * 4 + e;
+                                int c = wn * WN1 + ni * 16 + lo16;
                                 int cs = c ^ (((rl >> 2) & 3) << 4);
                                 scratch[rl * 64 + cs] =
                                     acc1[mi][ni][e] * sc3[ni] + bi3[ni];
@@ -284,7 +325,7 @@ __global__ __launch_bounds__(CH_TPB, WPS) void conv1x1_chain_kernel(
                     v += bf2f(rv[h][q]);
                     o[q] = f2bf(apply_act(v, act3));
                 }
-                const int r = h * 32 + e_rl;
+                const int r = h * ER + e_rl;
                 if (m0 + r < M)
                     store_bf16x8(Y + (long)(m0 + r) * N1 + j * 64 + e_c8, o);
                 // same 8 columns = one 16-B chunk of the A-operand layout
@@ -343,8 +384,8 @@ __global__ __launch_bounds__(CH_TPB, WPS) void conv1x1_chain_kernel(
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
 #pragma unroll
-        for (int i = 0; i < N2 / 32; ++i) {
-            int chunk = tid + i * CH_TPB;
+        for (int i = 0; i < N2 * 8 / TPB; ++i) {
+            int chunk = tid + i * TPB;
             int r = chunk / (N2 / 8);
             int c8 = (chunk % (N2 / 8)) * 8;
             bf16x8 o = load_bf16x8(obuf + r * OST + c8);
@@ -369,14 +410,15 @@ namespace {
 // launches unless forced.
 struct ChainWin { int K1, N1, N2; };
 const ChainWin kChainWins[] = {
-    // fused vs two launches, us, min..max of 3 repeats, batch 256 | 64
-    {64, 256, 64},     // 202..231 vs 355..359 | 47..48 vs 78..79
-    {64, 256, 128},    // 236..274 vs 438..448 | 65..66 vs 101..102
-    {128, 512, 128},   // 129..132 vs 257..258 | 35..35 vs 56..56
-    {128, 512, 256},   // 158..161 vs 313..313 | 43..44 vs 73..73
-    {256, 1024, 256},  // 135..136 vs 147..147 | 36..36 vs 42..43
-    // measured, not adopted (1 block/CU):
-    // {256, 1024, 512}   210..212 vs 212..212 | 55..55 vs 54..55
+    // fused vs two launches, us, min..max of 2 x 3 repeats, batch 256 | 64
+    {64, 256, 64},     // 189..219 vs 338..349 | 43..51 vs 73..80
+    {64, 256, 128},    // 222..228 vs 419..422 | 57..59 vs 99..101
+    {128, 512, 128},   // 124..127 vs 251..255 | 35..36 vs 56..57
+    {128, 512, 256},   // 155..158 vs 307..311 | 42..44 vs 72..72
+    // eight waves (four waves, one per SIMD: 134..136 | 36..37 and
+    // 207..213 | 55..56, the second a draw with two launches)
+    {256, 1024, 256},  // 111..118 vs 142..149 | 30..31 vs 42..43
+    {256, 1024, 512},  // 149..154 vs 207..211 | 37..40 vs 54..54
 };
 
 bool chain_policy(int K1, int N1, int N2) {
@@ -398,24 +440,31 @@ bool launch_conv1x1_chain(const void* x, const void* w3, const float* s3,
     const int mtiles = (M + CH_BM - 1) / CH_BM;
     const int a3 = relu3 ? ACT_RELU : ACT_NONE;
     const int a1 = relu1 ? ACT_RELU : ACT_NONE;
-#define CHAIN(K1v, N2v, WPSv)                                             \
+#define CHAIN(K1v, N2v, NWv, WPSv)                                        \
     do {                                                                  \
         int gx = 256 * WPSv;                                              \
         if (max_blocks > 0) gx = max_blocks;                              \
         if (gx > mtiles) gx = mtiles;                                     \
-        hipLaunchKernelGGL((conv1x1_chain_kernel<K1v, N2v, WPSv>),        \
-                           dim3(gx), dim3(CH_TPB), 0, s, (const bf16*)x,  \
-                           (const bf16*)w3, s3, b3, (const bf16*)res,     \
-                           (bf16*)y, (const bf16*)w1, s1, b1, (bf16*)a2,  \
-                           M, N1, a3, a1);                                \
+        /* one block per CU: the last round of tiles would leave most  */ \
+        /* CUs idle, so spread the same rounds evenly (784 tiles: 196  */ \
+        /* blocks x 4, not 256 blocks of which 16 run a fourth)        */ \
+        if (WPSv == 1 && max_blocks <= 0) {                               \
+            int rounds = (mtiles + gx - 1) / gx;                          \
+            gx = (mtiles + rounds - 1) / rounds;                          \
+        }                                                                 \
+        hipLaunchKernelGGL((conv1x1_chain_kernel<K1v, N2v, NWv, WPSv>),   \
+                           dim3(gx), dim3(NWv * WAVE), 0, s,              \
+                           (const bf16*)x, (const bf16*)w3, s3, b3,       \
+                           (const bf16*)res, (bf16*)y, (const bf16*)w1,   \
+                           s1, b1, (bf16*)a2, M, N1, a3, a1);             \
         return true;                                                      \
     } while (0)
-    if (K1 == 64 && N2 == 64) CHAIN(64, 64, 3);
-    if (K1 == 64 && N2 == 128) CHAIN(64, 128, 3);
-    if (K1 == 128 && N2 == 128) CHAIN(128, 128, 2);
-    if (K1 == 128 && N2 == 256) CHAIN(128, 256, 2);
-    if (K1 == 256 && N2 == 256) CHAIN(256, 256, 1);
-    if (K1 == 256 && N2 == 512) CHAIN(256, 512, 1);
+    if (K1 == 64 && N2 == 64) CHAIN(64, 64, 4, 3);
+    if (K1 == 64 && N2 == 128) CHAIN(64, 128, 4, 3);
+    if (K1 == 128 && N2 == 128) CHAIN(128, 128, 4, 2);
+    if (K1 == 128 && N2 == 256) CHAIN(128, 256, 4, 2);
+    if (K1 == 256 && N2 == 256) CHAIN(256, 256, 8, 1);
+    if (K1 == 256 && N2 == 512) CHAIN(256, 512, 8, 1);
 #undef CHAIN
     return false;
 }

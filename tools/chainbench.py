@@ -32,21 +32,22 @@ PAIR_CLASSES = [
 ]
 
 
-def time_mode(args, mode, iters):
+def time_mode(args, mode, iters, max_blocks=0):
     for _ in range(5):
-        ops.conv1x1_chain(*args, mode=mode)
+        ops.conv1x1_chain(*args, mode=mode, max_blocks=max_blocks)
     torch.cuda.synchronize()
     t0 = torch.cuda.Event(True)
     t1 = torch.cuda.Event(True)
     t0.record()
     for _ in range(iters):
-        ops.conv1x1_chain(*args, mode=mode)
+        ops.conv1x1_chain(*args, mode=mode, max_blocks=max_blocks)
     t1.record()
     torch.cuda.synchronize()
     return t0.elapsed_time(t1) * 1e3 / iters
 
 
-def bench_class(name, HW, K1, N1, N2, count, B, iters, repeats):
+def bench_class(name, HW, K1, N1, N2, count, B, iters, repeats,
+                max_blocks=0, fused_only=False):
     dev = "cuda:0"
     bf = torch.bfloat16
     x = torch.randn(B, HW, HW, K1, device=dev, dtype=bf)
@@ -58,18 +59,20 @@ def bench_class(name, HW, K1, N1, N2, count, B, iters, repeats):
     s1 = torch.rand(N2, device=dev) + 0.5
     b1 = torch.randn(N2, device=dev) * 0.1
     args = (x, w3, s3, b3, res, "relu", w1, s1, b1, "relu")
-    y1, a1 = ops.conv1x1_chain(*args, mode=1)
+    y1, a1 = ops.conv1x1_chain(*args, mode=1, max_blocks=max_blocks)
     y2, a2 = ops.conv1x1_chain(*args, mode=2)
     same = bool(torch.equal(y1, y2) and torch.equal(a1, a2))
     # alternate the modes so drift hits both alike
     fused, two = [], []
     for _ in range(repeats):
-        fused.append(time_mode(args, 1, iters))
-        two.append(time_mode(args, 2, iters))
+        fused.append(time_mode(args, 1, iters, max_blocks))
+        if not fused_only:
+            two.append(time_mode(args, 2, iters))
     M = B * HW * HW
     # bytes the fused kernel must move: x, res in; y, a2 out
     gb = M * (K1 + 2 * N1 + N2) * 2 / 1e9
     return dict(name=name, batch=B, M=M, pairs=count, bitwise=same,
+                max_blocks=max_blocks,
                 fused_us=[round(v, 1) for v in fused],
                 two_us=[round(v, 1) for v in two],
                 fused_tbps=round(gb / (min(fused) * 1e-6) / 1e3, 2))
@@ -80,16 +83,28 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[256, 64])
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--classes", nargs="+", default=None, metavar="K1-N1-N2",
+                    help="only the classes whose name contains one of these")
+    ap.add_argument("--max-blocks", type=int, nargs="+", default=[0],
+                    help="persistent-grid caps to time the fused kernel at "
+                         "(0 = the launcher's own grid)")
+    ap.add_argument("--fused-only", action="store_true",
+                    help="time only the fused kernel (counter runs: one "
+                         "kernel name in the profile)")
     args = ap.parse_args()
+    classes = [c for c in PAIR_CLASSES
+               if args.classes is None
+               or any(k in c[0] for k in args.classes)]
     rows = []
     for B in args.batches:
-        for c in PAIR_CLASSES:
-            r = bench_class(*c, B, args.iters, args.repeats)
+        for c, mb in [(c, mb) for c in classes for mb in args.max_blocks]:
+            r = bench_class(*c, B, args.iters, args.repeats, mb,
+                            args.fused_only)
             rows.append(r)
-            f, t = r["fused_us"], r["two_us"]
+            f, t = r["fused_us"], r["two_us"] or [float("nan")]
             verdict = ("WIN" if max(f) < min(t)
                        else "loss" if min(f) > max(t) else "noise")
-            print(f"b{B:<4d} {r['name']:18s} M={r['M']:7d} "
+            print(f"b{B:<4d} {r['name']:18s} M={r['M']:7d} mb={mb:<4d}"
                   f"fused {min(f):7.1f}..{max(f):7.1f} us  "
                   f"two {min(t):7.1f}..{max(t):7.1f} us  "
                   f"{r['fused_tbps']:5.2f} TB/s  bitwise={r['bitwise']}  "
