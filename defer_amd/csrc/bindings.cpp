@@ -244,9 +244,39 @@ Tensor linear_f32(const Tensor& x, const Tensor& w,
     return out;
 }
 
+// What the weight-stationary 3x3 path did, for tests: how many times the
+// kernel was launched in this process and the grid of the last launch.
+struct ConvWsStats {
+    std::mutex mu;
+    int64_t launches = 0;
+    int64_t blocks = 0, tiles_per_block = 0;
+};
+ConvWsStats& conv_ws_stats_ref() {
+    static ConvWsStats st;
+    return st;
+}
+
+py::dict conv_ws_stats() {
+    auto& st = conv_ws_stats_ref();
+    std::lock_guard<std::mutex> g(st.mu);
+    py::dict d;
+    d["launches"] = st.launches;
+    d["blocks"] = st.blocks;
+    d["tiles_per_block"] = st.tiles_per_block;
+    return d;
+}
+
+// mode selects between the weight-stationary kernel (conv_ws.hip) and the
+// launch_conv_igemm paths for the 3x3/s1/p1 64->64 bf16 class: 0 = the
+// measured policy, 1 = the new kernel wherever it covers the shape, 2 =
+// never. Shapes it does not cover run launch_conv_igemm under every mode.
+// max_blocks caps that kernel's grid (0 = policy).
 Tensor conv2d_bn_act(Tensor x, Tensor w, c10::optional<Tensor> scale,
                      c10::optional<Tensor> bias, c10::optional<Tensor> res,
-                     int64_t stride, int64_t pad, bool relu) {
+                     int64_t stride, int64_t pad, bool relu,
+                     int64_t mode = 0, int64_t max_blocks = 0) {
+    TORCH_CHECK(mode >= 0 && mode <= 2, "mode must be 0, 1 or 2");
+    TORCH_CHECK(max_blocks >= 0, "max_blocks must be >= 0");
     if (is_f32(x, "x"))
         return conv2d_bn_act_f32(x, w, scale, bias, res, stride, pad, relu);
     check_bf16(x, "x");
@@ -372,6 +402,17 @@ Tensor conv2d_bn_act(Tensor x, Tensor w, c10::optional<Tensor> scale,
     if (gemm_mode) {
         p.NB = (int)M; p.H = 1; p.W = 1; p.Cin = p.K;
         p.OH = 1; p.OW = 1;
+    }
+    if (mode != 2 && M > 0 && defer_hip::conv_ws_supported(p) &&
+        (mode == 1 || defer_hip::conv_ws_policy(p))) {
+        auto used = defer_hip::launch_conv_ws(p, relu, (bool)res,
+                                              (int)max_blocks, s);
+        auto& st = conv_ws_stats_ref();
+        std::lock_guard<std::mutex> g(st.mu);
+        ++st.launches;
+        st.blocks = used.blocks;
+        st.tiles_per_block = used.tiles_per_block;
+        return out;
     }
     defer_hip::launch_conv_igemm(p, relu, (bool)res, gemm_mode, false, s);
     return out;
@@ -933,7 +974,9 @@ Tensor lz4_decompress(Tensor comp, int64_t raw_len) {
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("conv2d_bn_act", &conv2d_bn_act, py::arg("x"), py::arg("w"),
           py::arg("scale"), py::arg("bias"), py::arg("res"),
-          py::arg("stride"), py::arg("pad"), py::arg("relu"));
+          py::arg("stride"), py::arg("pad"), py::arg("relu"),
+          py::arg("mode") = 0, py::arg("max_blocks") = 0);
+    m.def("conv_ws_stats", &conv_ws_stats);
     m.def("linear", &linear);
     m.def("bn_act", &bn_act);
     m.def("conv1x1_prebn", &conv1x1_prebn, py::arg("x"),

@@ -43,6 +43,24 @@ void launch_swin_repack_w(const void* w, void* wp, int Cout, int R,
 void launch_stem_repack_w(const void* w, void* wp, int Cout, int R, int S,
                           int C, int TR, hipStream_t s);
 
+// weight-stationary window kernel (conv_ws.hip): 3x3/s1/p1 convs with
+// Cin = Cout = 64 keep the whole weight tensor in registers and stage only
+// input windows to LDS; bit-identical to launch_conv_igemm on the same
+// ConvParams (relu or none, with or without residual).
+// conv_ws_supported: the kernel covers this geometry. conv_ws_policy: it
+// also measured faster than the paths of launch_conv_igemm for this shape
+// class (never when DEFER_CONV_VARIANT forces one of those).
+bool conv_ws_supported(const ConvParams& p);
+bool conv_ws_policy(const ConvParams& p);
+struct ConvWsLaunch {
+    int blocks;            // grid size
+    int tiles_per_block;   // 8x16 output tiles the busiest block walks
+};
+// max_blocks caps the grid (0 = the 512 resident blocks) so a few blocks
+// walk many tiles.
+ConvWsLaunch launch_conv_ws(const ConvParams& p, bool relu, bool has_res,
+                            int max_blocks, hipStream_t s);
+
 // fused pre-activation 1x1 conv: out = relu(x*ps+pb) @ w^T
 // (DenseNet BNActConv; bit-identical to bn_act -> conv GEMM mode)
 void launch_gemm_prebn(const void* x, const void* w, const float* ps,

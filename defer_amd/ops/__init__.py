@@ -59,14 +59,48 @@ def _backend(x: torch.Tensor):
     return None
 
 
+# A/B switch for the weight-stationary 3x3 kernel (same convention as
+# DEFER_CONV_CHAIN): unset = the launcher's measured policy, "0" = always
+# the older conv paths, "force" = the new kernel wherever it covers the
+# shape.
+_CONV_WS_MODES = {None: 0, "": 0, "force": 1, "0": 2}
+_conv_ws_env = os.environ.get("DEFER_CONV_WS")
+if _conv_ws_env not in _CONV_WS_MODES:
+    raise ValueError(
+        f"DEFER_CONV_WS={_conv_ws_env!r}: expected unset, '0' or 'force'")
+_CONV_WS_MODE = _CONV_WS_MODES[_conv_ws_env]
+
+
 def conv2d_bn_act(x, w, scale=None, bias=None, stride=1, padding=1,
-                  act="none", residual=None):
+                  act="none", residual=None, mode=None, max_blocks=0):
+    """act(conv2d(x, w) * scale + bias + residual), NHWC x and OHWI w.
+
+    On GPU, bf16 3x3/s1/p1 convs with 64 -> 64 channels can run the
+    weight-stationary window kernel (csrc/conv_ws.hip), whose output is
+    bit-identical to the general paths. mode: 0 = policy, 1 = that kernel
+    wherever it covers the shape, 2 = never; None = DEFER_CONV_WS. Every
+    other shape or dtype runs the general paths under every mode.
+    max_blocks caps that kernel's grid (0 = policy)."""
     m = _backend(x)
     if m is None:
         return _ref.conv2d_bn_act(x, w, scale, bias, stride, padding, act,
                                   residual)
     return m.conv2d_bn_act(x, w, scale, bias, residual, stride, padding,
-                           act == "relu")
+                           act == "relu",
+                           _CONV_WS_MODE if mode is None else mode,
+                           max_blocks)
+
+
+def conv_ws_stats():
+    """What the weight-stationary 3x3 path of conv2d_bn_act did in this
+    process: {"launches": kernel launches so far, "blocks",
+    "tiles_per_block": the grid of the last one}. Lets tests tell the new
+    kernel from the older paths, whose results are identical by design."""
+    m = _load_hip()
+    if m is None:
+        raise RuntimeError(
+            f"defer_amd HIP extension is not built: {_hip_err!r}")
+    return dict(m.conv_ws_stats())
 
 
 def conv1x1_prebn(x, w, scale, bias, out_scale=None, out_bias=None):

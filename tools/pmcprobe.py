@@ -18,6 +18,8 @@ SHAPES = {
     "l2res": (64, 28, 28, 128, 512, 1, 1, 0, True),
     "l3res": (64, 14, 14, 256, 1024, 1, 1, 0, True),
     "l1c1": (64, 56, 56, 64, 64, 1, 1, 0, False),
+    # layer1 3x3 at the bench batch (DEFER_CONV_WS=0 for the older kernel)
+    "l1c2": (256, 56, 56, 64, 64, 3, 1, 1, False),
 }
 
 
