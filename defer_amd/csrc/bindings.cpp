@@ -531,6 +531,82 @@ std::tuple<Tensor, Tensor> conv1x1_chain(
     return {y, a2};
 }
 
+// What the projected-residual chain kernel did, for tests: launches in
+// this process and the grid of the last one.
+struct ChainProjStats {
+    std::mutex mu;
+    int64_t launches = 0;
+    int64_t blocks = 0;
+};
+ChainProjStats& chain_proj_stats_ref() {
+    static ChainProjStats st;
+    return st;
+}
+
+py::dict chain_proj_stats() {
+    auto& st = chain_proj_stats_ref();
+    std::lock_guard<std::mutex> g(st.mu);
+    py::dict d;
+    d["launches"] = st.launches;
+    d["blocks"] = st.blocks;
+    return d;
+}
+
+// conv1x1_chain whose residual is bf16(conv1x1(xp, wp)*sp+bp), made inside
+// the kernel. mode 0: where the launcher's measured policy says so; 1:
+// wherever the kernel serves the shape. Returns nothing when no kernel was
+// launched: the caller then composes the projection conv and conv1x1_chain.
+c10::optional<std::tuple<Tensor, Tensor>> conv1x1_chain_proj(
+    Tensor x, Tensor w3, c10::optional<Tensor> s3, c10::optional<Tensor> b3,
+    Tensor xp, Tensor wp, c10::optional<Tensor> sp, c10::optional<Tensor> bp,
+    bool relu3, Tensor w1, c10::optional<Tensor> s1,
+    c10::optional<Tensor> b1, bool relu1, int64_t mode,
+    int64_t max_blocks) {
+    check_bf16(x, "x");
+    check_bf16(w3, "w3");
+    check_bf16(xp, "xp");
+    check_bf16(wp, "wp");
+    check_bf16(w1, "w1");
+    TORCH_CHECK(x.dim() == 4 && xp.dim() == 4 && w3.dim() == 4 &&
+                wp.dim() == 4 && w1.dim() == 4 && w3.size(1) == 1 &&
+                w3.size(2) == 1 && wp.size(1) == 1 && wp.size(2) == 1 &&
+                w1.size(1) == 1 && w1.size(2) == 1,
+                "conv1x1_chain_proj wants NHWC x and xp, 1x1 weights");
+    TORCH_CHECK(mode >= 0 && mode <= 1, "mode must be 0 or 1");
+    TORCH_CHECK(max_blocks >= 0, "max_blocks must be >= 0");
+    int NB = x.size(0), H = x.size(1), W = x.size(2), K1 = x.size(3);
+    int KP = xp.size(3);
+    int N1 = w3.size(0), N2 = w1.size(0);
+    TORCH_CHECK(w3.size(3) == K1 && w1.size(3) == N1 && wp.size(0) == N1 &&
+                wp.size(3) == KP, "channel mismatch");
+    TORCH_CHECK(xp.size(0) == NB && xp.size(1) == H && xp.size(2) == W,
+                "xp must cover the pixels of x");
+    TORCH_CHECK((!s3 || s3->numel() == N1) && (!b3 || b3->numel() == N1) &&
+                (!sp || sp->numel() == N1) && (!bp || bp->numel() == N1) &&
+                (!s1 || s1->numel() == N2) && (!b1 || b1->numel() == N2),
+                "scale/bias length must equal the conv's Cout");
+    long M = (long)NB * H * W;
+    TORCH_CHECK(M < (1LL << 31), "M too large");
+    if (K1 != 64 || KP != 64 || N2 != 64 || N1 % 64 != 0 || M == 0)
+        return c10::nullopt;
+    auto y = at::empty({NB, H, W, N1}, x.options());
+    auto a2 = at::empty({NB, H, W, N2}, x.options());
+    int blocks = defer_hip::launch_conv1x1_chain_proj(
+        bptr(x), bptr(w3), fptr_opt(s3, "s3", ones_buf(), N1),
+        fptr_opt(b3, "b3", zeros_buf(), N1), bptr(xp), bptr(wp),
+        fptr_opt(sp, "sp", ones_buf(), N1),
+        fptr_opt(bp, "bp", zeros_buf(), N1), bptr_mut(y), relu3, bptr(w1),
+        fptr_opt(s1, "s1", ones_buf(), N2),
+        fptr_opt(b1, "b1", zeros_buf(), N2), bptr_mut(a2), relu1, (int)M,
+        K1, KP, N1, N2, mode == 1, (int)max_blocks, cur_stream());
+    if (blocks == 0) return c10::nullopt;
+    auto& st = chain_proj_stats_ref();
+    std::lock_guard<std::mutex> g(st.mu);
+    ++st.launches;
+    st.blocks = blocks;
+    return std::make_tuple(y, a2);
+}
+
 Tensor bn_act(Tensor x, Tensor scale, Tensor bias, bool relu) {
     if (is_f32(x, "x")) {
         check_f32(x, "x");
@@ -987,6 +1063,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("s3"), py::arg("b3"), py::arg("res"), py::arg("relu3"),
           py::arg("w1"), py::arg("s1"), py::arg("b1"), py::arg("relu1"),
           py::arg("mode") = 0, py::arg("max_blocks") = 0);
+    m.def("conv1x1_chain_proj", &conv1x1_chain_proj, py::arg("x"),
+          py::arg("w3"), py::arg("s3"), py::arg("b3"), py::arg("xp"),
+          py::arg("wp"), py::arg("sp"), py::arg("bp"), py::arg("relu3"),
+          py::arg("w1"), py::arg("s1"), py::arg("b1"), py::arg("relu1"),
+          py::arg("mode") = 0, py::arg("max_blocks") = 0);
+    m.def("chain_proj_stats", &chain_proj_stats);
     m.def("conv_bn_act_maxpool", &conv_bn_act_maxpool, py::arg("x"),
           py::arg("w"), py::arg("scale"), py::arg("bias"),
           py::arg("stride"), py::arg("pad"), py::arg("relu"),

@@ -39,11 +39,26 @@
 // last LDS write of its phase: the compiler drains pending LDS DMA in
 // front of LDS stores. Co-resident blocks cover the rest.
 //
+// PROJ (K1 = 64, N2 = 64, four waves): the residual is not a tensor but the
+// block's 1x1 projection shortcut, RES = bf16((XP[M,64] @ WP[N1,64]^T) * sp
+// + bp), which the kernel makes per chunk: a third GEMM of GEMM1's size on
+// the same fragment mapping, so a lane holds acc1 and the shortcut for the
+// same (row, column) and adds them in front of the bounce. Its operands go
+// from global straight to registers (XP fragments once per tile, issued
+// under the a2 stores; WP fragments, sp and bp a chunk ahead); nothing of
+// it touches LDS. With no residual stream to wait behind, W1(j+1) is staged
+// together with W3(j+1) into a second W1 slice (48 KiB, still three blocks
+// a CU), and a chunk waits for memory once, at its top.
+//
 // Bit-identity: GEMM1 accumulates k ascending with the igemm 16x16x32
 // fragment mapping and the same epilogue expression; GEMM2 consumes the
 // bf16-rounded y, j ascending and k ascending inside a chunk — the same
 // per-element order as a standalone GEMM-mode launch. Both outputs match
-// the two-launch path bit for bit (tests/test_conv_chain_gpu.py).
+// the two-launch path bit for bit (tests/test_conv_chain_gpu.py). PROJ's
+// shortcut is one k-tile, ks ascending, then acc * sp + bp rounded to bf16,
+// as the projection's own GEMM-mode launch stores it, and it enters y by
+// the same fp32 add as a loaded residual
+// (tests/test_conv_chain_proj_gpu.py).
 #include "common.h"
 #include "kernels.h"
 
@@ -61,18 +76,22 @@ __device__ __forceinline__ void ch_glds16(const bf16* src, bf16* lds_base) {
         16, 0, 0);
 }
 
-template <int K1, int N2, int NW, int WPS>
+template <int K1, int N2, int NW, int WPS, bool PROJ = false>
 __global__ __launch_bounds__(NW * WAVE, WPS) void conv1x1_chain_kernel(
     const bf16* __restrict__ X,      // [M][K1]
     const bf16* __restrict__ W3,     // [N1][K1]
     const float* __restrict__ S3,    // [N1]
     const float* __restrict__ B3,    // [N1]
-    const bf16* __restrict__ RES,    // [M][N1]
+    const bf16* __restrict__ RES,    // [M][N1] (unused with PROJ)
     bf16* __restrict__ Y,            // [M][N1]
     const bf16* __restrict__ W1,     // [N2][N1]
     const float* __restrict__ S1,    // [N2]
     const float* __restrict__ B1,    // [N2]
     bf16* __restrict__ A2,           // [M][N2]
+    const bf16* __restrict__ XP,     // PROJ: [M][64] shortcut input
+    const bf16* __restrict__ WP,     // PROJ: [N1][64]
+    const float* __restrict__ SP,    // PROJ: [N1]
+    const float* __restrict__ BP,    // PROJ: [N1]
     int M, int N1, int act3, int act1) {
     constexpr int TPB = NW * WAVE;
     constexpr bool DEEP = NW == 8;           // two waves per SIMD, one block
@@ -89,16 +108,26 @@ __global__ __launch_bounds__(NW * WAVE, WPS) void conv1x1_chain_kernel(
     constexpr int NR = CH_BM / ER;           // epilogue-1 rounds
     constexpr int SCR = ER * 64 * 2;         // fp32 bounce, in bf16 units
     static_assert(NW == 4 || NW == 8, "2 x 2 or 2 x 4 waves");
+    static_assert(!PROJ || (K1 == 64 && NW == 4),
+                  "the projected residual is built for the K1 = 64 class");
     static_assert(CH_BM * OST <= N2 * 64 + SCR + CH_YT, "out-bounce fits");
+    // PROJ keeps two W1 slices (48 KiB in all, still three blocks a CU):
+    // W1(j+1) is staged with W3(j+1), a chunk ahead, into the slice GEMM2(j)
+    // does not read, so no stage is waited for in the middle of a chunk.
+    // Its out-bounce lies in the fp32 bounce and the y-tile, clear of both
+    // slices
+    constexpr int W1S = PROJ ? 2 : 1;
+    static_assert(!PROJ || CH_BM * OST <= SCR + CH_YT, "out-bounce fits");
 
     __shared__ __attribute__((aligned(16)))
-    bf16 lds[CH_BM * K1 + 64 * K1 + N2 * 64 + SCR + CH_YT];
+    bf16 lds[CH_BM * K1 + 64 * K1 + W1S * N2 * 64 + SCR + CH_YT];
     bf16* Ap = lds;                          // NK1 tiles [64][64]
     bf16* W3b = Ap + CH_BM * K1;             // NK1 tiles [64 n][64 k]
-    bf16* W1b = W3b + 64 * K1;               // [N2][64]
-    float* scratch = (float*)(W1b + N2 * 64);
-    bf16* ytile = W1b + N2 * 64 + SCR;
-    bf16* obuf = W1b;                        // epilogue 2: W1b..ytile end
+    bf16* W1b = W3b + 64 * K1;               // W1S x [N2][64]
+    float* scratch = (float*)(W1b + W1S * N2 * 64);
+    bf16* ytile = W1b + W1S * N2 * 64 + SCR;
+    // epilogue 2: W1b..ytile end (PROJ: scratch..ytile end)
+    bf16* obuf = PROJ ? (bf16*)scratch : W1b;
 
     const int tid = threadIdx.x;
     const int wave = tid / WAVE;
@@ -141,7 +170,7 @@ __global__ __launch_bounds__(NW * WAVE, WPS) void conv1x1_chain_kernel(
                           W3b + kt * 4096 + (wave * (64 * CPT) + i * 64) * 8);
         }
     };
-    auto stage_w1 = [&](int j) {
+    auto stage_w1 = [&](int j, int slice) {
 #pragma unroll
         for (int i = 0; i < CPT; ++i) {
             const bf16* src =
@@ -149,7 +178,8 @@ __global__ __launch_bounds__(NW * WAVE, WPS) void conv1x1_chain_kernel(
 #pragma unroll
             for (int t = 0; t < NT2; ++t)
                 ch_glds16(src + (long)t * 64 * N1,
-                          W1b + t * 4096 + (wave * (64 * CPT) + i * 64) * 8);
+                          W1b + slice * (N2 * 64) + t * 4096
+                              + (wave * (64 * CPT) + i * 64) * 8);
         }
     };
 
@@ -189,7 +219,46 @@ __global__ __launch_bounds__(NW * WAVE, WPS) void conv1x1_chain_kernel(
         }
     };
     bf16x8 rvn[NR];
-    res_load(rvn, mt * CH_BM, 0);
+    // PROJ: the residual is (XP @ WP^T) * sp + bp rounded to bf16, made
+    // here. Operand fragments go straight from global to registers in the
+    // GEMM1 mapping: XP once per tile, WP / sp / bp one chunk ahead
+    bf16x8 xpf[2][2], wpf[NI1][2];
+    float spn[NI1], bpn[NI1];
+    auto xp_load = [&](int m0) {
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) {
+            int m = m0 + wm * 32 + mi * 16 + lo16;
+            if (m >= M) m = M - 1;           // clamped rows are never stored
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+                xpf[mi][ks] =
+                    load_bf16x8(XP + (long)m * 64 + (ks * 4 + hi4) * 8);
+        }
+    };
+    auto wp_load = [&](int j) {
+#pragma unroll
+        for (int ni = 0; ni < NI1; ++ni) {
+            int n = j * 64 + wn * WN1 + ni * 16 + lo16;
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+                wpf[ni][ks] =
+                    load_bf16x8(WP + (long)n * 64 + (ks * 4 + hi4) * 8);
+        }
+    };
+    int w1s = 0;                             // PROJ: slice GEMM2 reads
+    if constexpr (PROJ) {
+        stage_w1(0, 0);
+        xp_load(mt * CH_BM);
+        wp_load(0);
+#pragma unroll
+        for (int ni = 0; ni < NI1; ++ni) {
+            int n = wn * WN1 + ni * 16 + lo16;
+            spn[ni] = SP[n];
+            bpn[ni] = BP[n];
+        }
+    } else {
+        res_load(rvn, mt * CH_BM, 0);
+    }
 
     for (; mt < mtiles; mt += gridDim.x) {
         const int m0 = mt * CH_BM;
@@ -216,9 +285,43 @@ __global__ __launch_bounds__(NW * WAVE, WPS) void conv1x1_chain_kernel(
             // across the back edge, waits there for vmcnt(0): the W3 stage
             // and the residual load would drain in the middle of GEMM2
             bf16x8 rv[NR];
+            // PROJ: XP, WP(j), sp/bp(j) landed with the wait above. One
+            // k-tile, ks ascending, then the igemm epilogue expression and
+            // its bf16 round: the value the projection launch would store
+            // (kept as bf16 pairs: 8 registers across GEMM1, not 16)
+            u32 rp[2][NI1][2];
+            if constexpr (PROJ) {
+                f32x4 accp[2][NI1];
+#pragma unroll
+                for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                    for (int ni = 0; ni < NI1; ++ni)
+                        accp[mi][ni] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                        for (int ni = 0; ni < NI1; ++ni)
+                            accp[mi][ni] = MFMA_BF16_16x16x32(
+                                xpf[mi][ks], wpf[ni][ks], accp[mi][ni]);
+#pragma unroll
+                for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                    for (int ni = 0; ni < NI1; ++ni)
+#pragma unroll
+                        for (int e = 0; e < 4; e += 2) {
+                            bf16x2 t;
+                            t[0] = f2bf(accp[mi][ni][e] * spn[ni] + bpn[ni]);
+                            t[1] = f2bf(accp[mi][ni][e + 1] * spn[ni]
+                                        + bpn[ni]);
+                            rp[mi][ni][e / 2] = __builtin_bit_cast(u32, t);
+                        }
+            }
 #pragma unroll
             for (int h = 0; h < NR; ++h) {
-                if constexpr (DEEP) {
+                if constexpr (PROJ) {
+                } else if constexpr (DEEP) {
                     u32x4 t = __builtin_bit_cast(u32x4, rvn[h]), c;
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
@@ -243,12 +346,25 @@ __global__ __launch_bounds__(NW * WAVE, WPS) void conv1x1_chain_kernel(
                 int n = jn * 64 + wn * WN1 + ni * 16 + lo16;
                 sc3n[ni] = S3[n];
                 bi3n[ni] = B3[n];
+                if constexpr (PROJ) {
+                    spn[ni] = SP[n];
+                    bpn[ni] = BP[n];
+                }
             }
-            stage_w1(j);
-            // exactly NR loads, unconditionally, AFTER the W1 stage: the
-            // counted wait in front of epilogue 1 lets them stay in flight
-            res_load(rvn, (j + 1 < NJ || !more) ? m0 : m0 + (int)gridDim.x
-                                                          * CH_BM, jn);
+            if constexpr (PROJ) {
+                // W1(j) is in its slice already (staged a chunk ago); the
+                // WP fragments of the next chunk take the registers the
+                // projection GEMM above has just read, and nothing in this
+                // chunk waits for them
+                wp_load(jn);
+            } else {
+                stage_w1(j, 0);
+                // exactly NR loads, unconditionally, AFTER the W1 stage:
+                // the counted wait in front of epilogue 1 lets them stay
+                // in flight
+                res_load(rvn, (j + 1 < NJ || !more)
+                                  ? m0 : m0 + (int)gridDim.x * CH_BM, jn);
+            }
 
             // ---- GEMM1: acc1[64x64] = Apanel @ W3_j^T (igemm mapping)
             f32x4 acc1[2][NI1];
@@ -287,12 +403,17 @@ __global__ __launch_bounds__(NW * WAVE, WPS) void conv1x1_chain_kernel(
             // chunk, issued after it, may stay in flight. A panel and W3b
             // are free after the barrier; DEEP has nothing to free here
             // (W3b is restaged two barriers later) and lets the bounce's
-            // own barrier publish W1(j)
-            if constexpr (NR == 2)
+            // own barrier publish W1(j). PROJ waits for nothing here: its
+            // W1(j) landed at the chunk top, and W3b and the W1 slices are
+            // restaged only behind the bounce's barriers, which every wave
+            // reaches after its GEMM1 reads
+            if constexpr (PROJ)
+                ;
+            else if constexpr (NR == 2)
                 asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
             else
                 asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
-            if constexpr (!DEEP) __builtin_amdgcn_s_barrier();
+            if constexpr (!DEEP && !PROJ) __builtin_amdgcn_s_barrier();
 
             // ---- epilogue 1: NR rounds of ER rows through the fp32
             // bounce; the waves whose slab lies in the round write it
@@ -308,8 +429,15 @@ __global__ __launch_bounds__(NW * WAVE, WPS) void conv1x1_chain_kernel(
                                 int rl = wm * 32 % ER + mi * 16 + hi4 * 4 + e;
                                 int c = wn * WN1 + ni * 16 + lo16;
                                 int cs = c ^ (((rl >> 2) & 3) << 4);
-                                scratch[rl * 64 + cs] =
-                                    acc1[mi][ni][e] * sc3[ni] + bi3[ni];
+                                float v = acc1[mi][ni][e] * sc3[ni] + bi3[ni];
+                                // the same fp32 add of the same operands
+                                // as the reading side's below
+                                if constexpr (PROJ)
+                                    v += __builtin_bit_cast(
+                                        float,
+                                        e % 2 ? rp[mi][ni][e / 2] & 0xffff0000u
+                                              : rp[mi][ni][e / 2] << 16);
+                                scratch[rl * 64 + cs] = v;
                             }
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -322,7 +450,7 @@ __global__ __launch_bounds__(NW * WAVE, WPS) void conv1x1_chain_kernel(
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     float v = q < 4 ? v0[q] : v1[q - 4];
-                    v += bf2f(rv[h][q]);
+                    if constexpr (!PROJ) v += bf2f(rv[h][q]);
                     o[q] = f2bf(apply_act(v, act3));
                 }
                 const int r = h * ER + e_rl;
@@ -338,7 +466,10 @@ __global__ __launch_bounds__(NW * WAVE, WPS) void conv1x1_chain_kernel(
             // pending LDS DMA before any ds_write, so staging earlier
             // would only stall the bounce. GEMM2 (LDS reads only) is its
             // latency cover.
-            if (j + 1 < NJ || more) stage_w3(jn);
+            if (j + 1 < NJ || more) {
+                stage_w3(jn);
+                if constexpr (PROJ) stage_w1(jn, w1s ^ 1);
+            }
 
             // ---- GEMM2: acc2[64 x N2] += ytile @ W1_j^T
 #pragma unroll
@@ -354,13 +485,15 @@ __global__ __launch_bounds__(NW * WAVE, WPS) void conv1x1_chain_kernel(
                 for (int ni = 0; ni < NI2; ++ni) {
                     int row = wn * WN2 + ni * 16 + lo16;
                     bf16x8 bfr = *reinterpret_cast<bf16x8*>(
-                        W1b + row * 64 + ch_swz(row, ks * 4 + hi4) * 8);
+                        W1b + (PROJ ? w1s * (N2 * 64) : 0) + row * 64
+                            + ch_swz(row, ks * 4 + hi4) * 8);
 #pragma unroll
                     for (int mi = 0; mi < 2; ++mi)
                         acc2[mi][ni] = MFMA_BF16_16x16x32(af[mi], bfr,
                                                           acc2[mi][ni]);
                 }
             }
+            if constexpr (PROJ) w1s ^= 1;
         }
 
         // ---- epilogue 2: s1/b1 + act1 on the accumulator, bf16 bounce
@@ -381,6 +514,8 @@ __global__ __launch_bounds__(NW * WAVE, WPS) void conv1x1_chain_kernel(
         // next tile's A panel: after the last LDS write of this tile
         // (see the W3 note), under the out-bounce reads and a2 stores
         if (more) stage_a(mt + gridDim.x);
+        if constexpr (PROJ)
+            if (more) xp_load((mt + (int)gridDim.x) * CH_BM);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
 #pragma unroll
@@ -456,7 +591,9 @@ bool launch_conv1x1_chain(const void* x, const void* w3, const float* s3,
                            dim3(gx), dim3(NWv * WAVE), 0, s,              \
                            (const bf16*)x, (const bf16*)w3, s3, b3,       \
                            (const bf16*)res, (bf16*)y, (const bf16*)w1,   \
-                           s1, b1, (bf16*)a2, M, N1, a3, a1);             \
+                           s1, b1, (bf16*)a2, (const bf16*)nullptr,       \
+                           (const bf16*)nullptr, (const float*)nullptr,   \
+                           (const float*)nullptr, M, N1, a3, a1);         \
         return true;                                                      \
     } while (0)
     if (K1 == 64 && N2 == 64) CHAIN(64, 64, 4, 3);
@@ -467,6 +604,36 @@ bool launch_conv1x1_chain(const void* x, const void* w3, const float* s3,
     if (K1 == 256 && N2 == 512) CHAIN(256, 512, 8, 1);
 #undef CHAIN
     return false;
+}
+
+int launch_conv1x1_chain_proj(const void* x, const void* w3, const float* s3,
+                              const float* b3, const void* xp,
+                              const void* wp, const float* sp,
+                              const float* bp, void* y, bool relu3,
+                              const void* w1, const float* s1,
+                              const float* b1, void* a2, bool relu1, int M,
+                              int K1, int KP, int N1, int N2, bool force,
+                              int max_blocks, hipStream_t s) {
+    if (M <= 0 || N1 < 64 || N1 % 64 != 0) return 0;
+    if (K1 != 64 || KP != 64 || N2 != 64) return 0;
+    const int mtiles = (M + CH_BM - 1) / CH_BM;
+    // Policy: the measured class, at every size. Kernel vs the projection
+    // launch plus the chain launch (tools/chainbench.py, us, min..max of
+    // 2 x 3 repeats): batch 256 222..278 vs 342..358, batch 64 52..54 vs
+    // 82..83, batch 16 24..24 vs 30..31, batch 8 13..14 vs 20..20, batch 1
+    // (49 tiles) 8.5..9.4 vs 12.1..12.3: no tile-count gate
+    if (!force && N1 != 256) return 0;
+    int gx = 256 * 3;
+    if (max_blocks > 0) gx = max_blocks;
+    if (gx > mtiles) gx = mtiles;
+    hipLaunchKernelGGL((conv1x1_chain_kernel<64, 64, 4, 3, true>), dim3(gx),
+                       dim3(4 * WAVE), 0, s, (const bf16*)x,
+                       (const bf16*)w3, s3, b3, (const bf16*)nullptr,
+                       (bf16*)y, (const bf16*)w1, s1, b1, (bf16*)a2,
+                       (const bf16*)xp, (const bf16*)wp, sp, bp, M, N1,
+                       relu3 ? ACT_RELU : ACT_NONE,
+                       relu1 ? ACT_RELU : ACT_NONE);
+    return gx;
 }
 
 }  // namespace defer_hip

@@ -82,6 +82,20 @@ bool launch_conv1x1_chain(const void* x, const void* w3, const float* s3,
                           const float* b1, void* a2, bool relu1, int M,
                           int K1, int N1, int N2, bool force,
                           int max_blocks, hipStream_t s);
+// the same pair with a projected residual made inside the kernel:
+//   res = bf16((xp[M,KP] @ wp[N1,KP]^T) * sp + bp)
+// in place of a res tensor; bit-identical to a GEMM-mode launch_conv_igemm
+// for res followed by launch_conv1x1_chain. Serves K1 = KP = N2 = 64 (the
+// ResNet layer1 shortcut); without force only the measured class, N1 =
+// 256. Returns the grid it launched, 0 when it launched nothing.
+int launch_conv1x1_chain_proj(const void* x, const void* w3, const float* s3,
+                              const float* b3, const void* xp,
+                              const void* wp, const float* sp,
+                              const float* bp, void* y, bool relu3,
+                              const void* w1, const float* s1,
+                              const float* b1, void* a2, bool relu1, int M,
+                              int K1, int KP, int N1, int N2, bool force,
+                              int max_blocks, hipStream_t s);
 
 // fused stem (stem_pool.hip): 7x7/s2/p3 Cin=3 Cout=64 conv + folded BN +
 // ReLU + 3x3/s2/p1 max-pool, writing only the pooled tensor; bit-identical

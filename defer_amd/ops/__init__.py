@@ -9,8 +9,8 @@ equivalent substrate was TensorFlow's native kernels, node.py:106).
 GPU tensors may be bf16 (the tuned default) or fp32 (the exact-f32 MFMA
 path, `csrc/conv_f32.hip` + `csrc/ops_f32.hip`); the bindings pick the
 launcher from the tensor's dtype and raise for anything else. The fused
-ops (`conv1x1_prebn`, `conv1x1_chain`, `conv_bn_act_maxpool`) have no fp32
-kernel: for fp32 GPU tensors they compose the primitive ops of this module,
+ops (`conv1x1_prebn`, `conv1x1_chain`, `conv1x1_chain_proj`,
+`conv_bn_act_maxpool`) have no fp32 kernel: for fp32 GPU tensors they compose the primitive ops of this module,
 which is the same arithmetic the CPU branch runs.
 
 On CPU, ops use the fp32 PyTorch reference implementations (tests and the
@@ -159,6 +159,62 @@ def conv1x1_chain(x, w3, s3, b3, residual, act3, w1, s1, b1, act1,
     return m.conv1x1_chain(x, w3, s3, b3, residual, act3 == "relu", w1, s1,
                            b1, act1 == "relu",
                            _CHAIN_MODE if mode is None else mode, max_blocks)
+
+
+# A/B switch for the chain kernel that makes the projection shortcut itself
+# (same convention as DEFER_CONV_CHAIN): unset = the launcher's measured
+# policy, "0" = always the projection launch plus conv1x1_chain, "force" =
+# the kernel wherever it serves the shape.
+_CHAIN_PROJ_MODES = {None: 0, "": 0, "force": 1, "0": 2}
+_chain_proj_env = os.environ.get("DEFER_CHAIN_PROJ")
+if _chain_proj_env not in _CHAIN_PROJ_MODES:
+    raise ValueError(
+        f"DEFER_CHAIN_PROJ={_chain_proj_env!r}: expected unset, '0' or "
+        f"'force'")
+_CHAIN_PROJ_MODE = _CHAIN_PROJ_MODES[_chain_proj_env]
+
+
+def conv1x1_chain_proj(x, w3, s3, b3, xp, wp, sp, bp, act3, w1, s1, b1,
+                       act1, mode=None, max_blocks=0):
+    """conv1x1_chain whose residual is a 1x1/s1 projection of xp (the
+    first bottleneck of a ResNet stage with stride 1):
+
+        res = conv1x1(xp, wp)*sp + bp
+        y   = act3(conv1x1(x, w3)*s3 + b3 + res)
+        a2  = act1(conv1x1(y, w1)*s1 + b1)
+
+    Returns (y, a2), identical to conv2d_bn_act for res followed by
+    conv1x1_chain. On GPU, for 64-channel x and xp and a 64-channel a2, one
+    kernel (csrc/chain.hip, PROJ) makes res per tile in registers, so res is
+    neither written nor read back. Every other shape, fp32 and the CPU
+    compose the two ops. mode: 0 = policy, 1 = the kernel wherever it serves
+    the shape, 2 = never; None = DEFER_CHAIN_PROJ."""
+    if mode is None:
+        mode = _CHAIN_PROJ_MODE
+    if mode not in (0, 1, 2):
+        raise ValueError(f"mode={mode!r}: expected 0, 1 or 2")
+    if x.is_cuda and x.dtype == torch.bfloat16 and mode != 2:
+        if act3 not in ("relu", "none") or act1 not in ("relu", "none"):
+            raise ValueError("act3/act1: expected 'relu' or 'none'")
+        out = _backend(x).conv1x1_chain_proj(
+            x, w3, s3, b3, xp, wp, sp, bp, act3 == "relu", w1, s1, b1,
+            act1 == "relu", mode, max_blocks)
+        if out is not None:
+            return out
+    res = conv2d_bn_act(xp, wp, sp, bp, 1, 0, "none")
+    return conv1x1_chain(x, w3, s3, b3, res, act3, w1, s1, b1, act1)
+
+
+def chain_proj_stats():
+    """What conv1x1_chain_proj did in this process: {"launches": launches
+    of the projected-residual kernel so far, "blocks": the grid of the last
+    one}. Lets tests tell that kernel from the composed ops, whose results
+    are identical by design."""
+    m = _load_hip()
+    if m is None:
+        raise RuntimeError(
+            f"defer_amd HIP extension is not built: {_hip_err!r}")
+    return dict(m.chain_proj_stats())
 
 
 # A/B switch for the fused stem conv + max-pool kernel (same convention as

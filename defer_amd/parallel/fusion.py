@@ -14,6 +14,11 @@ block's 1x1 conv1 (ops.conv1x1_chain): add_k is the widest tensor of the
 block and conv1 reads it straight back, so one kernel computes both and
 add_k is never re-read.
 
+fuse_chain_projection then folds a 1x1/s1 projection shortcut (res2_0_proj
+of the ResNets) into that chained node (ops.conv1x1_chain_proj): the kernel
+makes the shortcut from the block input per tile, and the projection's
+output, as wide as add_k, is neither written nor read.
+
 A third pass, fuse_conv_pool, merges a conv whose only consumer is a
 max-pool into one node (ops.conv_bn_act_maxpool): for the 7x7/s2 stem of
 the ResNets and DenseNet121 the HIP kernel then writes only the pooled
@@ -164,6 +169,69 @@ def fuse_expand_reduce(graph: LayerGraph) -> LayerGraph:
                                list(n.inputs), dict(n.kwargs)))
         nodes.append(GraphNode(n.name, _Pick(0), [pair]))
         nodes.append(GraphNode(c.name, _Pick(1), [pair]))
+    return LayerGraph(nodes, output=graph.output)
+
+
+class ChainedExpandReduceProj(ChainedExpandReduce):
+    """ChainedExpandReduce whose skip is a 1x1/s1 projection conv of xp
+    (the first block of a stride-1 stage): the projection joins the call
+    (ops.conv1x1_chain_proj), so its output is never a tensor of its own.
+    .proj is the original module, shared like .expand and .reduce."""
+
+    def __init__(self, expand: FusedConvAddAct, reduce: ConvBNAct,
+                 proj: ConvBNAct):
+        super().__init__(expand, reduce)
+        self.proj = proj
+
+    def forward(self, x, xp):
+        from defer_amd import ops
+
+        c3, c1, cp = self.expand.conv, self.reduce, self.proj
+        return ops.conv1x1_chain_proj(
+            x, c3.weight.to(x.dtype), c3.scale, c3.bias, xp,
+            cp.weight.to(x.dtype), cp.scale, cp.bias, self.expand.act,
+            c1.weight.to(x.dtype), c1.scale, c1.bias, c1.act)
+
+
+def fuse_chain_projection(graph: LayerGraph) -> LayerGraph:
+    """Fold a projection shortcut into its ChainedExpandReduce node: the
+    node's residual input must be a 1x1/s1/p0 ConvBNAct without activation
+    that takes one input, feeds this node and nothing else and is not the
+    graph output. The node then takes [b, the projection's input] and the
+    projection's node goes; names, picks and the two other modules stay.
+    A stride-2 projection, one with another consumer and one whose add is
+    not chained (its conv1 lives in the next stage) are left alone."""
+    consumers = {}
+    for n in graph.nodes:
+        for p in n.inputs:
+            consumers.setdefault(p, []).append(n)
+    by_name = {n.name: n for n in graph.nodes}
+
+    folded = {}                        # chain node name -> proj node
+    for n in graph.nodes:
+        if not (type(n.layer) is ChainedExpandReduce and len(n.inputs) == 2
+                and not n.kwargs):
+            continue
+        p = by_name.get(n.inputs[1])
+        if (p is not None and type(p.layer) is ConvBNAct
+                and _is_pointwise(p.layer) and p.layer.act == "none"
+                and len(p.inputs) == 1 and not p.kwargs
+                and consumers.get(p.name, []) == [n]
+                and p.name != graph.output):
+            folded[n.name] = p
+    gone = {p.name for p in folded.values()}
+
+    nodes: List[GraphNode] = []
+    for n in graph.nodes:
+        if n.name in gone:
+            continue
+        p = folded.get(n.name)
+        if p is None:
+            nodes.append(n)
+            continue
+        layer = ChainedExpandReduceProj(n.layer.expand, n.layer.reduce,
+                                        p.layer)
+        nodes.append(GraphNode(n.name, layer, [n.inputs[0], p.inputs[0]]))
     return LayerGraph(nodes, output=graph.output)
 
 

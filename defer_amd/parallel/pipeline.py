@@ -65,13 +65,14 @@ class StageExecutor:
                  use_graph: bool = False, fuse: bool = True,
                  chain: bool = True):
         if fuse:
-            from defer_amd.parallel.fusion import (fuse_conv_pool,
+            from defer_amd.parallel.fusion import (fuse_chain_projection,
+                                                   fuse_conv_pool,
                                                    fuse_expand_reduce,
                                                    fuse_residual_adds)
 
             g = fuse_residual_adds(stage.graph)
             if chain:
-                g = fuse_expand_reduce(g)
+                g = fuse_chain_projection(fuse_expand_reduce(g))
             g = fuse_conv_pool(g)
             stage = GraphModel(g, name=stage.model_name)
         self.model = stage

@@ -7,6 +7,10 @@ two conv launches) using device events, at batch 256 (the 1-GPU bench)
 and batch 64 (the multi-stage micro-batch). A class belongs in the
 launcher's policy table only if fused beats two-launch by more than the
 spread of the repeats.
+
+The last class, "L1 proj+64-256-64", is ops.conv1x1_chain_proj: mode=1 (the
+chain kernel that makes the res2_0 projection shortcut itself) against
+mode=2 (the projection launch plus the chain launch).
 """
 
 import argparse
@@ -78,6 +82,62 @@ def bench_class(name, HW, K1, N1, N2, count, B, iters, repeats,
                 fused_tbps=round(gb / (min(fused) * 1e-6) / 1e3, 2))
 
 
+PROJ_CLASS = ("L1 proj+64-256-64", 56, 64, 256, 64, 1)
+
+
+def bench_proj(name, HW, K1, N1, N2, count, B, iters, repeats,
+               max_blocks=0, fused_only=False):
+    """ops.conv1x1_chain_proj: mode=1 (the shortcut made inside the chain
+    kernel) against mode=2 (the projection launch plus the chain launch)."""
+    dev = "cuda:0"
+    bf = torch.bfloat16
+    x = torch.randn(B, HW, HW, K1, device=dev, dtype=bf)
+    xp = torch.randn(B, HW, HW, 64, device=dev, dtype=bf)
+    w3 = torch.randn(N1, 1, 1, K1, device=dev, dtype=bf) * 0.05
+    wp = torch.randn(N1, 1, 1, 64, device=dev, dtype=bf) * 0.05
+    w1 = torch.randn(N2, 1, 1, N1, device=dev, dtype=bf) * 0.05
+    s3, sp = (torch.rand(N1, device=dev) + 0.5 for _ in range(2))
+    b3, bp = (torch.randn(N1, device=dev) * 0.1 for _ in range(2))
+    s1 = torch.rand(N2, device=dev) + 0.5
+    b1 = torch.randn(N2, device=dev) * 0.1
+    args = (x, w3, s3, b3, xp, wp, sp, bp, "relu", w1, s1, b1, "relu")
+
+    def run(mode, mb=0):
+        return ops.conv1x1_chain_proj(*args, mode=mode, max_blocks=mb)
+
+    def time_it(mode, mb=0):
+        for _ in range(5):
+            run(mode, mb)
+        torch.cuda.synchronize()
+        t0 = torch.cuda.Event(True)
+        t1 = torch.cuda.Event(True)
+        t0.record()
+        for _ in range(iters):
+            run(mode, mb)
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1) * 1e3 / iters
+
+    n0 = ops.chain_proj_stats()["launches"]
+    y1, a1 = run(1, max_blocks)
+    assert ops.chain_proj_stats()["launches"] == n0 + 1
+    y2, a2 = run(2)
+    same = bool(torch.equal(y1, y2) and torch.equal(a1, a2))
+    fused, two = [], []
+    for _ in range(repeats):
+        fused.append(time_it(1, max_blocks))
+        if not fused_only:
+            two.append(time_it(2))
+    M = B * HW * HW
+    # bytes the fused kernel must move: x, xp in; y, a2 out
+    gb = M * (K1 + 64 + N1 + N2) * 2 / 1e9
+    return dict(name=name, batch=B, M=M, pairs=count, bitwise=same,
+                max_blocks=max_blocks,
+                fused_us=[round(v, 1) for v in fused],
+                two_us=[round(v, 1) for v in two],
+                fused_tbps=round(gb / (min(fused) * 1e-6) / 1e3, 2))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[256, 64])
@@ -92,14 +152,14 @@ def main():
                     help="time only the fused kernel (counter runs: one "
                          "kernel name in the profile)")
     args = ap.parse_args()
-    classes = [c for c in PAIR_CLASSES
+    classes = [c for c in PAIR_CLASSES + [PROJ_CLASS]
                if args.classes is None
                or any(k in c[0] for k in args.classes)]
     rows = []
     for B in args.batches:
         for c, mb in [(c, mb) for c in classes for mb in args.max_blocks]:
-            r = bench_class(*c, B, args.iters, args.repeats, mb,
-                            args.fused_only)
+            bench = bench_proj if c is PROJ_CLASS else bench_class
+            r = bench(*c, B, args.iters, args.repeats, mb, args.fused_only)
             rows.append(r)
             f, t = r["fused_us"], r["two_us"] or [float("nan")]
             verdict = ("WIN" if max(f) < min(t)
