@@ -12,6 +12,7 @@
 #include <string>
 #include <unordered_map>
 
+#include "conv_plan.h"
 #include "kernels.h"
 
 namespace {
@@ -266,6 +267,156 @@ py::dict conv_ws_stats() {
     return d;
 }
 
+// The one place that fills the ConvParams geometry (pointers stay null).
+// gemm_mode collapses a 1x1/s1/p0 conv or a linear layer to
+// out[M,N] = x[M,K] @ w[N,K]^T.
+ConvParams conv_geom(long M, int K, int Cout, int NB, int H, int W, int Cin,
+                     int OH, int OW, int R, int S, int stride, int pad,
+                     bool gemm_mode) {
+    ConvParams p{};
+    p.M = (int)M; p.K = K; p.Cout = Cout;
+    p.NB = NB; p.H = H; p.W = W; p.Cin = Cin;
+    p.OH = OH; p.OW = OW; p.R = R; p.S = S;
+    p.stride = stride; p.pad = pad;
+    if (gemm_mode) {
+        p.NB = (int)M; p.H = 1; p.W = 1; p.Cin = K;
+        p.OH = 1; p.OW = 1;
+    }
+    return p;
+}
+
+// Which way a bf16 conv goes and the geometry its kernel sees. Decided
+// from the shapes alone: no allocation, no launch.
+struct ConvPrep {
+    enum Path { SWIN, STEM, PAD8, GENERAL } path = GENERAL;
+    ConvParams p{};                 // geometry of the launch
+    bool gemm_mode = false, stem_mode = false;
+    int OH = 0, OW = 0;
+    int C8 = 0;                     // SWIN, PAD8: padded channel count
+    int Kpad = 0;                   // SWIN: padded K of the repacked weights
+    int TR = 0, PH = 0, PW = 0;     // STEM (Keff is p.K)
+};
+
+ConvPrep prepare_conv(int NB, int H, int W, int Cin, int Cout, int R, int S,
+                      int stride, int pad, bool has_res, char variant) {
+    ConvPrep g;
+    int OH = g.OH = (H + 2 * pad - R) / stride + 1;
+    int OW = g.OW = (W + 2 * pad - S) / stride + 1;
+    long M = (long)NB * OH * OW;
+    TORCH_CHECK(M < (1LL << 31), "M too large");
+    if (Cin % 8 == 0) {
+        g.gemm_mode = (R == 1 && S == 1 && stride == 1 && pad == 0);
+        g.p = conv_geom(M, R * S * Cin, Cout, NB, H, W, Cin, OH, OW, R, S,
+                        stride, pad, g.gemm_mode);
+        return g;
+    }
+    // small-Cin window path (VGG-style 3x3 stems): channel-pad to
+    // 8, repack weights j-major (cached), stage each 8x16 output
+    // tile's input window to LDS once — kills the ~9x input
+    // re-reads of the channel-pad gather path (b1.c1 143 -> 91 us).
+    // The 7x7/s2 ResNet stem stays on the spatial-prepad run-packed
+    // path: its K is 168 vs the window kernel's zero-padded 448
+    // (Cin 3 -> 8), and the 2.7x extra MFMA work measured slower.
+    if (!has_res && R == S && R == 3 && (stride == 1 || stride == 2) &&
+        Cout == 64) {
+        ConvParams q = conv_geom(M, R * S * 8, Cout, NB, H, W, 8, OH, OW,
+                                 R, S, stride, pad, false);
+        if (defer_hip::plan_swin(q, variant).grid_x) {
+            g.path = ConvPrep::SWIN;
+            g.p = q;
+            g.C8 = 8;
+            g.Kpad = (R * R * 8 + 63) / 64 * 64;
+            return g;
+        }
+    }
+    if ((stride * Cin) % 2 == 0) {
+        // STEM path (ResNet 7x7/s2, Cin=3): spatially pre-pad the
+        // raw input and gather K as (r, run)-major where a run is
+        // TR = ceil(S*Cin/8)*8 CONTIGUOUS bf16 of one padded input
+        // row (S*Cin real + a few next-pixel values that multiply
+        // zero weights). K drops from R*S*pad8(Cin) (392) to R*TR
+        // (168) and the gather needs no validity math at all.
+        int TR = (S * Cin + 7) / 8 * 8;
+        int Keff = R * TR;
+        int nk = (Keff + 63) / 64;
+        int rmax = (nk * 64 - 1) / TR;          // last k row touched
+        int PW = std::max(W + 2 * pad,
+                          (OW - 1) * stride + (TR + Cin - 1) / Cin);
+        int PH = std::max(H + 2 * pad, (OH - 1) * stride + rmax + 1);
+        if (((long)PW * Cin) % 2) PW += 1;      // 4-B chunk alignment
+        g.path = ConvPrep::STEM;
+        g.stem_mode = true;
+        g.TR = TR; g.PH = PH; g.PW = PW;
+        // S carries the run length TR
+        g.p = conv_geom(M, Keff, Cout, NB, PH, PW, Cin, OH, OW, R, TR,
+                        stride, 0, false);
+        return g;
+    }
+    // odd stride*Cin (e.g. 3x3/s1 VGG stem): zero-pad channels to 8
+    // and take the regular implicit-GEMM path.
+    g.path = ConvPrep::PAD8;
+    g.C8 = (Cin + 7) / 8 * 8;
+    g.p = conv_geom(M, R * S * g.C8, Cout, NB, H, W, g.C8, OH, OW, R, S,
+                    stride, pad, false);
+    return g;
+}
+
+// The kernel plan of a prepared conv. Only the general path may take the
+// weight-stationary kernel.
+defer_hip::ConvPlan plan_prepared(const ConvPrep& g, int64_t mode,
+                                  int64_t max_blocks, char variant) {
+    if (g.path == ConvPrep::SWIN) return defer_hip::plan_swin(g.p, variant);
+    return defer_hip::plan_conv(
+        g.p, g.gemm_mode, g.stem_mode,
+        g.path == ConvPrep::GENERAL ? (int)mode : 2, (int)max_blocks,
+        variant);
+}
+
+// What conv2d_bn_act (4-D shapes) or linear (2-D shapes) would launch for
+// these shapes: the path, the prepared geometry, the plan and the kernel's
+// template arguments. Runs prepare_conv and the plan and nothing else, so
+// it needs no GPU. variant: a DEFER_CONV_VARIANT value, None = the latched
+// environment value.
+py::dict conv_plan(std::vector<int64_t> xs, std::vector<int64_t> ws,
+                   int64_t stride, int64_t pad, bool has_res, int64_t mode,
+                   int64_t max_blocks, c10::optional<std::string> variant) {
+    using namespace pybind11::literals;
+    TORCH_CHECK(mode >= 0 && mode <= 2, "mode must be 0, 1 or 2");
+    TORCH_CHECK(max_blocks >= 0, "max_blocks must be >= 0");
+    const char v = variant ? (variant->empty() ? '\0' : (*variant)[0])
+                           : defer_hip::conv_variant();
+    ConvPrep g;
+    const bool is_linear = xs.size() == 2 && ws.size() == 2;
+    if (is_linear) {
+        TORCH_CHECK(ws[1] == xs[1], "K mismatch");
+        g.gemm_mode = true;
+        g.p = conv_geom(xs[0], (int)xs[1], (int)ws[0], 0, 0, 0, 0, 0, 0, 1,
+                        1, 1, 0, true);
+        mode = 2;
+    } else {
+        TORCH_CHECK(xs.size() == 4, "x must be NHWC");
+        TORCH_CHECK(ws.size() == 4, "w must be OHWI");
+        TORCH_CHECK(ws[3] == xs[3], "w Cin mismatch");
+        g = prepare_conv((int)xs[0], (int)xs[1], (int)xs[2], (int)xs[3],
+                         (int)ws[0], (int)ws[1], (int)ws[2], (int)stride,
+                         (int)pad, has_res, v);
+    }
+    static const char* paths[] = {"swin", "stem", "pad8", "general"};
+    static const char* families[] = {"igemm", "win", "ws", "swin"};
+    const auto pl = plan_prepared(g, mode, max_blocks, v);
+    return py::dict(
+        "path"_a = is_linear ? "linear" : paths[g.path], "M"_a = g.p.M,
+        "K"_a = g.p.K, "Cin"_a = g.p.Cin, "C8"_a = g.C8, "Kpad"_a = g.Kpad,
+        "TR"_a = g.TR, "PH"_a = g.PH, "PW"_a = g.PW,
+        "family"_a = families[pl.family], "amode"_a = pl.amode,
+        "bp"_a = (bool)pl.bp, "BM"_a = pl.BM, "BN"_a = pl.BN,
+        "DA"_a = pl.DA, "DB"_a = pl.DB, "WPS"_a = pl.WPS, "TH"_a = pl.TH,
+        "full_sync"_a = pl.full_sync, "grid_x"_a = pl.grid_x,
+        "grid_y"_a = pl.grid_y, "blocks"_a = pl.blocks,
+        "tiles_per_block"_a = pl.tiles_per_block,
+        "template_args"_a = defer_hip::conv_kernel_args(pl, has_res));
+}
+
 // mode selects between the weight-stationary kernel (conv_ws.hip) and the
 // launch_conv_igemm paths for the 3x3/s1/p1 64->64 bf16 class: 0 = the
 // measured policy, 1 = the new kernel wherever it covers the shape, 2 =
@@ -286,135 +437,67 @@ Tensor conv2d_bn_act(Tensor x, Tensor w, c10::optional<Tensor> scale,
     int NB = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3);
     int Cout = w.size(0), R = w.size(1), S = w.size(2);
     TORCH_CHECK(w.size(3) == Cin, "w Cin mismatch");
-    int OH = (int)((H + 2 * pad - R) / stride + 1);
-    int OW = (int)((W + 2 * pad - S) / stride + 1);
-    long M = (long)NB * OH * OW;
-    TORCH_CHECK(M < (1LL << 31), "M too large");
-    auto out = at::empty({NB, OH, OW, Cout}, x.options());
+    const char variant = defer_hip::conv_variant();
+    const ConvPrep g = prepare_conv(NB, H, W, Cin, Cout, R, S, (int)stride,
+                                    (int)pad, (bool)res, variant);
+    auto out = at::empty({NB, g.OH, g.OW, Cout}, x.options());
     if (res) check_bf16(*res, "res");
     hipStream_t s = cur_stream();
 
-    ConvParams p{};
+    ConvParams p = g.p;
     p.scale = fptr_opt(scale, "scale", ones_buf(), Cout);
     p.bias = fptr_opt(bias, "bias", zeros_buf(), Cout);
     p.res = res ? bptr(*res) : nullptr;
     p.out = bptr_mut(out);
     p.zbuf = zero_buf();
-    p.M = (int)M;
-    p.Cout = Cout;
 
-    if (Cin % 8 != 0) {
-        // small-Cin window path (VGG-style 3x3 stems): channel-pad to
-        // 8, repack weights j-major (cached), stage each 8x16 output
-        // tile's input window to LDS once — kills the ~9x input
-        // re-reads of the channel-pad gather path (b1.c1 143 -> 91 us).
-        // The 7x7/s2 ResNet stem stays on the spatial-prepad run-packed
-        // path: its K is 168 vs the window kernel's zero-padded 448
-        // (Cin 3 -> 8), and the 2.7x extra MFMA work measured slower.
-        if (!res && R == S && R == 3 &&
-            (stride == 1 || stride == 2) && Cout == 64) {
-            int Kpad = (R * R * 8 + 63) / 64 * 64;
-            auto xp = at::empty({NB, H, W, 8}, x.options());
-            defer_hip::launch_pad_channels(bptr(x), bptr_mut(xp),
-                                           (long)NB * H * W, Cin, 8, s);
-            auto wp = cached_weight_prep(w, 1000 + Kpad, [&] {
-                auto t = at::empty({Cout, Kpad}, w.options());
-                defer_hip::launch_swin_repack_w(bptr(w), bptr_mut(t),
-                                               Cout, R, Cin, Kpad, s);
-                return t;
-            });
-            ConvParams q = p;
-            q.x = bptr(xp);
-            q.w = bptr(wp);
-            q.NB = NB; q.H = H; q.W = W; q.Cin = 8;
-            q.OH = OH; q.OW = OW; q.R = R; q.S = S;
-            q.stride = (int)stride; q.pad = (int)pad;
-            q.K = R * S * 8;
-            if (defer_hip::launch_conv_swin(q, relu, R, (int)stride, s))
-                return out;
-        }
-        if ((stride * Cin) % 2 == 0) {
-            // STEM path (ResNet 7x7/s2, Cin=3): spatially pre-pad the
-            // raw input and gather K as (r, run)-major where a run is
-            // TR = ceil(S*Cin/8)*8 CONTIGUOUS bf16 of one padded input
-            // row (S*Cin real + a few next-pixel values that multiply
-            // zero weights). K drops from R*S*pad8(Cin) (392) to R*TR
-            // (168) and the gather needs no validity math at all.
-            int TR = (S * Cin + 7) / 8 * 8;
-            int Keff = R * TR;
-            int nk = (Keff + 63) / 64;
-            int rmax = (nk * 64 - 1) / TR;          // last k row touched
-            int PW = std::max(W + 2 * (int)pad,
-                              (OW - 1) * (int)stride
-                                  + (TR + Cin - 1) / Cin);
-            int PH = std::max(H + 2 * (int)pad,
-                              (OH - 1) * (int)stride + rmax + 1);
-            if (((long)PW * Cin) % 2) PW += 1;      // 4-B chunk alignment
-            auto xp = at::empty({NB, PH, PW, Cin}, x.options());
-            defer_hip::launch_pad2d(bptr(x), bptr_mut(xp), NB, H, W, Cin,
-                                    PH, PW, (int)pad, (int)pad, s);
-            auto wp = cached_weight_prep(w, TR, [&] {
-                auto t = at::empty({Cout, Keff}, w.options());
-                defer_hip::launch_stem_repack_w(bptr(w), bptr_mut(t),
-                                                Cout, R, S, Cin, TR, s);
-                return t;
-            });
-            p.x = bptr(xp);
-            p.w = bptr(wp);
-            p.K = Keff;
-            p.NB = NB; p.H = PH; p.W = PW; p.Cin = Cin;
-            p.OH = OH; p.OW = OW; p.R = R;
-            p.S = TR;                   // S carries the run length TR
-            p.stride = (int)stride; p.pad = 0;
-            defer_hip::launch_conv_igemm(p, relu, (bool)res, false, true,
-                                         s);
-            return out;
-        }
-        // odd stride*Cin (e.g. 3x3/s1 VGG stem): zero-pad channels to 8
-        // and take the regular implicit-GEMM path.
-        int C8 = (Cin + 7) / 8 * 8;
-        auto xp = at::empty({NB, H, W, C8}, x.options());
+    Tensor xp = x, wp = w;
+    if (g.path == ConvPrep::SWIN) {
+        xp = at::empty({NB, H, W, 8}, x.options());
         defer_hip::launch_pad_channels(bptr(x), bptr_mut(xp),
-                                       (long)NB * H * W, Cin, C8, s);
-        auto wp = cached_weight_prep(w, -C8, [&] {
-            auto t = at::empty({Cout, R, S, C8}, w.options());
-            defer_hip::launch_pad_channels(bptr(w), bptr_mut(t),
-                                           (long)Cout * R * S, Cin, C8, s);
+                                       (long)NB * H * W, Cin, 8, s);
+        wp = cached_weight_prep(w, 1000 + g.Kpad, [&] {
+            auto t = at::empty({Cout, g.Kpad}, w.options());
+            defer_hip::launch_swin_repack_w(bptr(w), bptr_mut(t), Cout, R,
+                                            Cin, g.Kpad, s);
             return t;
         });
-        p.x = bptr(xp);
-        p.w = bptr(wp);
-        p.K = R * S * C8;
-        p.NB = NB; p.H = H; p.W = W; p.Cin = C8;
-        p.OH = OH; p.OW = OW; p.R = R; p.S = S;
-        p.stride = (int)stride; p.pad = (int)pad;
-        defer_hip::launch_conv_igemm(p, relu, (bool)res, false, false, s);
-        return out;
+    } else if (g.path == ConvPrep::STEM) {
+        xp = at::empty({NB, g.PH, g.PW, Cin}, x.options());
+        defer_hip::launch_pad2d(bptr(x), bptr_mut(xp), NB, H, W, Cin, g.PH,
+                                g.PW, (int)pad, (int)pad, s);
+        wp = cached_weight_prep(w, g.TR, [&] {
+            auto t = at::empty({Cout, p.K}, w.options());
+            defer_hip::launch_stem_repack_w(bptr(w), bptr_mut(t), Cout, R,
+                                            S, Cin, g.TR, s);
+            return t;
+        });
+    } else if (g.path == ConvPrep::PAD8) {
+        xp = at::empty({NB, H, W, g.C8}, x.options());
+        defer_hip::launch_pad_channels(bptr(x), bptr_mut(xp),
+                                       (long)NB * H * W, Cin, g.C8, s);
+        wp = cached_weight_prep(w, -g.C8, [&] {
+            auto t = at::empty({Cout, R, S, g.C8}, w.options());
+            defer_hip::launch_pad_channels(bptr(w), bptr_mut(t),
+                                           (long)Cout * R * S, Cin, g.C8,
+                                           s);
+            return t;
+        });
     }
-
-    p.x = bptr(x);
-    p.w = bptr(w);
-    p.K = R * S * Cin;
-    p.NB = NB; p.H = H; p.W = W; p.Cin = Cin;
-    p.OH = OH; p.OW = OW; p.R = R; p.S = S;
-    p.stride = (int)stride; p.pad = (int)pad;
-    bool gemm_mode = (R == 1 && S == 1 && stride == 1 && pad == 0);
-    if (gemm_mode) {
-        p.NB = (int)M; p.H = 1; p.W = 1; p.Cin = p.K;
-        p.OH = 1; p.OW = 1;
-    }
-    if (mode != 2 && M > 0 && defer_hip::conv_ws_supported(p) &&
-        (mode == 1 || defer_hip::conv_ws_policy(p))) {
+    p.x = bptr(xp);
+    p.w = bptr(wp);
+    const auto plan = plan_prepared(g, mode, max_blocks, variant);
+    if (plan.family == defer_hip::ConvPlan::WS) {
         auto used = defer_hip::launch_conv_ws(p, relu, (bool)res,
                                               (int)max_blocks, s);
         auto& st = conv_ws_stats_ref();
-        std::lock_guard<std::mutex> g(st.mu);
+        std::lock_guard<std::mutex> g2(st.mu);
         ++st.launches;
         st.blocks = used.blocks;
         st.tiles_per_block = used.tiles_per_block;
         return out;
     }
-    defer_hip::launch_conv_igemm(p, relu, (bool)res, gemm_mode, false, s);
+    defer_hip::launch_conv_igemm(p, plan, relu, (bool)res, s);
     return out;
 }
 
@@ -432,15 +515,14 @@ Tensor linear(Tensor x, Tensor w, c10::optional<Tensor> bias) {
         bias_f = cached_weight_prep(*bias, -1, [&] {
             return bias->to(at::kFloat).contiguous();
         });
-    ConvParams p{};
+    ConvParams p = conv_geom(M, K, N, 0, 0, 0, 0, 0, 0, 1, 1, 1, 0, true);
     p.x = bptr(x); p.w = bptr(w);
     p.scale = fptr_opt(c10::nullopt, "scale", ones_buf(), N);
     p.bias = fptr_opt(bias_f, "bias", zeros_buf(), N);
     p.res = nullptr; p.out = bptr_mut(out); p.zbuf = zero_buf();
-    p.M = M; p.K = K; p.Cout = N;
-    p.NB = M; p.H = 1; p.W = 1; p.Cin = K;
-    p.OH = 1; p.OW = 1; p.R = 1; p.S = 1; p.stride = 1; p.pad = 0;
-    defer_hip::launch_conv_igemm(p, false, false, true, false, cur_stream());
+    const auto plan = defer_hip::plan_conv(p, true, false, 2, 0,
+                                           defer_hip::conv_variant());
+    defer_hip::launch_conv_igemm(p, plan, false, false, cur_stream());
     return out;
 }
 
@@ -1053,6 +1135,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("stride"), py::arg("pad"), py::arg("relu"),
           py::arg("mode") = 0, py::arg("max_blocks") = 0);
     m.def("conv_ws_stats", &conv_ws_stats);
+    m.def("conv_plan", &conv_plan, py::arg("x_shape"), py::arg("w_shape"),
+          py::arg("stride"), py::arg("pad"), py::arg("has_res"),
+          py::arg("mode") = 0, py::arg("max_blocks") = 0,
+          py::arg("variant") = py::none());
+    m.def("conv_table_rows", &defer_hip::conv_table_rows);
     m.def("linear", &linear);
     m.def("bn_act", &bn_act);
     m.def("conv1x1_prebn", &conv1x1_prebn, py::arg("x"),

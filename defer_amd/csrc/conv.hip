@@ -1,6 +1,6 @@
 // Convolution kernels for gfx950 (CDNA4), NHWC bf16, MFMA 16x16x32
 // with fp32 accumulation. Three kernel families, selected by a measured
-// per-shape policy in launch_conv_igemm (docs/OPTIMIZATION_LOG.md has
+// per-shape policy in plan_conv, conv_plan.h (docs/OPTIMIZATION_LOG.md has
 // the A/B numbers behind every choice):
 //
 //   conv_igemm_kernel — implicit GEMM, the general path (1x1s, deep-K
@@ -52,14 +52,13 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "conv_plan.h"
 
 using defer_hip::ConvParams;
 
 #define BK 64
 #define NTHREADS 256
 #define KCH (BK / 8)          // 16-B chunks per tile row (8)
-
-enum { AMODE_GEMM = 0, AMODE_CONV = 1, AMODE_RSC = 2, AMODE_STEM = 3 };
 
 // XOR swizzle: logical (row, k8) lives at physical k8p = k8 ^ (row & 7).
 __device__ __forceinline__ int swz(int row, int k8) {
@@ -1248,271 +1247,86 @@ static u32 magic32(u32 d) {          // ceil(2^32 / d), d > 1
     return d <= 1 ? 0u : (u32)(((1ull << 32) + d - 1) / d);
 }
 
-void launch_conv_igemm(const ConvParams& p0, bool relu, bool has_res,
-                       bool gemm_mode, bool stem_mode, hipStream_t s) {
+// The dispatch table: exactly the instantiations the plans of conv_plan.h
+// can name (the invariants there say what is left out). A row lists its
+// template arguments after ACT, HAS_RES once; the key, the printed name
+// and the four (act, res) kernels all come from that one token list.
+typedef void (*ConvKernel)(ConvParams);
+template <int ACT, bool, int R, int STRIDE>   // conv_swin_kernel has no RES
+constexpr ConvKernel swin_kernel = conv_swin_kernel<ACT, R, STRIDE>;
+struct ConvRow {
+    ConvPlan::Family family;
+    const char* args;
+    std::array<int, 7> key;
+    ConvKernel kernel[2][2];   // [relu][has_res]
+};
+#define ROW(F, K, ...)                                                    \
+    {ConvPlan::F, #__VA_ARGS__, {{__VA_ARGS__}},                          \
+     {{K<ACT_NONE, false, __VA_ARGS__>, K<ACT_NONE, true, __VA_ARGS__>},  \
+      {K<ACT_RELU, false, __VA_ARGS__>, K<ACT_RELU, true, __VA_ARGS__>}}}
+// a tile config without B_PERSIST serves all four gathers; with it (K
+// fits one tile) only GEMM and CONV
+#define IGEMM_ROWS(...)                                                   \
+    ROW(IGEMM, conv_igemm_kernel, AMODE_GEMM, false, __VA_ARGS__),        \
+    ROW(IGEMM, conv_igemm_kernel, AMODE_CONV, false, __VA_ARGS__),        \
+    ROW(IGEMM, conv_igemm_kernel, AMODE_RSC, false, __VA_ARGS__),         \
+    ROW(IGEMM, conv_igemm_kernel, AMODE_STEM, false, __VA_ARGS__)
+#define IGEMM_ROWS_BP(...)                                                \
+    ROW(IGEMM, conv_igemm_kernel, AMODE_GEMM, true, __VA_ARGS__),         \
+    ROW(IGEMM, conv_igemm_kernel, AMODE_CONV, true, __VA_ARGS__)
+static const ConvRow conv_rows[] = {
+    //             BM,  BN, DA, DB, WPS
+    IGEMM_ROWS_BP(128, 64, 4, 2, 2),
+    IGEMM_ROWS(128, 64, 3, 3, 2),
+    IGEMM_ROWS_BP(128, 64, 3, 3, 2),   // legacy
+    IGEMM_ROWS(128, 128, 2, 2, 2),
+    IGEMM_ROWS(64, 128, 3, 3, 2),
+    IGEMM_ROWS_BP(64, 64, 4, 2, 4),
+    IGEMM_ROWS(64, 64, 3, 3, 3),
+    IGEMM_ROWS_BP(64, 64, 4, 2, 2),
+    IGEMM_ROWS(64, 64, 3, 3, 2),
+    IGEMM_ROWS_BP(64, 64, 3, 3, 2),    // legacy
+    ROW(WIN, conv_win_kernel, 64, 8, 256, 2),   // BN, TH, TPB, WPS
+    ROW(WIN, conv_win_kernel, 64, 4, 256, 2),
+    ROW(SWIN, swin_kernel, 3, 1),               // R, stride
+    ROW(SWIN, swin_kernel, 3, 2),
+};
+static const char* const family_names[] = {"igemm", "win", "ws", "swin"};
+
+static const ConvRow& find_row(const ConvPlan& pl) {
+    for (const ConvRow& r : conv_rows)
+        if (r.family == pl.family && r.key == plan_key(pl)) return r;
+    throw std::runtime_error("no kernel for this plan: " + to_string(pl));
+}
+
+std::string conv_kernel_args(const ConvPlan& pl, bool has_res) {
+    const char* res = has_res ? "true" : "false";
+    if (pl.family == ConvPlan::WS) return res;   // conv_ws_kernel<ACT, RES>
+    if (pl.family == ConvPlan::SWIN) return find_row(pl).args;
+    return std::string(res) + ", " + find_row(pl).args;
+}
+
+std::vector<std::string> conv_table_rows() {
+    std::vector<std::string> rows;
+    for (const ConvRow& r : conv_rows)
+        rows.push_back(std::string(family_names[r.family]) + ": " + r.args);
+    return rows;
+}
+
+void launch_conv_igemm(const ConvParams& p0, const ConvPlan& pl, bool relu,
+                       bool has_res, hipStream_t s) {
+    static_assert(CONV_BK == BK && WIN_TW == WTW, "conv_plan.h tile sizes");
     ConvParams p = p0;
-    p.owmul = magic32((u32)p.OW);
-    p.ohmul = magic32((u32)p.OH);
-    p.cmul = magic32((u32)p.Cin);
-    p.smul = magic32((u32)p.S);
-    const int nk = (p.K + BK - 1) / BK;
-    const bool bp = (nk == 1) && !stem_mode;
-    const bool rsc = !gemm_mode && !stem_mode && !bp &&
-                     (p.Cin % 64 == 0) && (p.R * p.S <= 32);
-    const int amode = stem_mode ? AMODE_STEM
-                                : gemm_mode ? AMODE_GEMM
-                                            : (rsc ? AMODE_RSC
-                                                   : AMODE_CONV);
-    // tile selection. BN128 halves A re-staging and doubles MFMA per
-    // staged byte; memory-bound small-K shapes keep the 3-deep BN64
-    // pipeline. BM=64 for small-M shapes (more blocks on the 256 CUs).
-    // DEFER_CONV_VARIANT=legacy reverts to the symmetric-depth policy
-    // (A/B comparison harness).
-    // variants: default = measured policy; "legacy" = symmetric-depth
-    // policy pre-v2; "small" = force the high-occupancy small-tile
-    // config everywhere it is legal (experiment harness)
-    static const char variant = [] {
-        const char* e = getenv("DEFER_CONV_VARIANT");
-        return e ? e[0] : '\0';
-    }();
-    const bool legacy = variant == 'l';
-    const bool force_small = variant == 's';
-    const bool force_win = variant == 'w' || variant == 'W';
-    // variant 'W': force win AND full vmcnt(0) drains (debug)
-
-    // window-reuse path: 3x3/s1/p1 with TH x 16 output tiles (TH 8 or
-    // 4); stages each input window once per 64-channel block instead of
-    // once per (r,s) k-tile (9x less A traffic into LDS). Partial tiles
-    // are handled (zero-filled windows, guarded stores) but waste
-    // compute; require <= ~18% padding overhead. Cout>128 shapes
-    // (56x56x256-class) stay on the BN128 RSC config: the BN64 window
-    // kernel pays 2-4x the B re-staging (measured loss) and a BN128
-    // window instantiation spills ~250 B/lane at this register budget.
-    // Cout <= 128 only. Wider variants were all built and measured
-    // slower than the BN128 RSC config they would replace: BN128 x 4
-    // waves spills ~250 B/lane; BN128 x 512 threads at 4 waves/SIMD
-    // spills ~200 B/lane; at 2 waves/SIMD it runs ONE 8-wave block per
-    // CU and loses the cross-block epilogue overlap (b3 179 -> 211 us,
-    // same failure mode as the BM256 implicit-GEMM tile).
-    const bool win_ok =
-        (!legacy && !force_small) && !gemm_mode && !stem_mode &&
-        p.R == 3 && p.S == 3 && p.stride == 1 && p.pad == 1 &&
-        (p.Cin % 64 == 0) && (p.Cout % 64 == 0) && p.Cout <= 128;
-    auto win_fit = [&](int TH) {
-        long th = (p.OH + TH - 1) / TH, tw = (p.OW + WTW - 1) / WTW;
-        if (th * TH * tw * WTW * 100 > (long)p.OH * p.OW * 118)
-            return false;
-        return force_win ||
-               (long)p.NB * th * tw * ((p.Cout + 127) / 128) >= 512;
-    };
-    // TH=4 measured slower than the BN128 RSC config on the 28-px
-    // shapes it would serve (2x B re-staging + 14% tile waste), so the
-    // default policy uses TH=8 only; TH=4 stays exercised by the forced
-    // numerics harness (tools/wincheck.py)
-    const int THsel = !win_ok          ? 0
-                      : win_fit(8)     ? 8
-                      : (force_win && win_fit(4)) ? 4
-                                       : 0;
-    if (THsel) {
-        const int BNw = 64;
-        const long wth = (p.OH + THsel - 1) / THsel;
-        const long wtw = (p.OW + WTW - 1) / WTW;
-        const int mt2 = (int)((long)p.NB * wth * wtw);
-        const int nyw = p.Cout / BNw;
-        int gxw = mt2;
-        if ((long)mt2 * nyw > 768) {
-            gxw = 768 / nyw > 0 ? 768 / nyw : 1;
-            if (gxw > mt2) gxw = mt2;
-        }
-        p.smul = (variant == 'W') ? 1u : 0u;   // full-sync debug flag
-        dim3 gw(gxw, nyw), bw(NTHREADS);
-#define WIN_TILE(A, RZ, BNv, TPBv, WPSv)                                  \
-    hipLaunchKernelGGL((conv_win_kernel<A, RZ, BNv, 8, TPBv, WPSv>), gw,  \
-                       bw, 0, s, p)
-#define WIN_BN(A, RZ)                                                     \
-    do {                                                                  \
-        if (THsel == 8) WIN_TILE(A, RZ, 64, 256, 2);                      \
-        else hipLaunchKernelGGL((conv_win_kernel<A, RZ, 64, 4>), gw, bw,  \
-                                0, s, p);                                 \
-    } while (0)
-        if (relu) {
-            if (has_res) WIN_BN(ACT_RELU, true);
-            else WIN_BN(ACT_RELU, false);
-        } else {
-            if (has_res) WIN_BN(ACT_NONE, true);
-            else WIN_BN(ACT_NONE, false);
-        }
-#undef WIN_BN
-#undef WIN_TILE
-        return;
+    if (pl.family != ConvPlan::SWIN) {
+        p.owmul = magic32((u32)p.OW);
+        p.ohmul = magic32((u32)p.OH);
+        p.cmul = magic32((u32)p.Cin);
+        p.smul = magic32((u32)p.S);
     }
-    const int mt128 = (p.M + 127) / 128;
-    int BMsel, BNsel;
-    const bool deepK = p.K >= 1024;
-    // 1x1 convs (any stride — stride-2 projections gather via AMODE_RSC
-    // but share the GEMM arithmetic shape) follow the GEMM policy.
-    const bool one1 = gemm_mode || (p.R == 1 && p.S == 1 && p.pad == 0);
-    // 1x1 shapes with K>=512: wide n-tile (halves A re-staging; measured
-    // −10…14% on the L3/L4 1x1s; K=128/256 shapes regress with BN128 —
-    // epilogue-frequency-bound — and keep BN64)
-    const bool wide = (deepK || (!legacy && one1 && !bp &&
-                                 p.K >= 512)) &&
-                      p.Cout >= 128;
-    // pure-bandwidth 1x1s (K<=256): small tiles + 3-4 blocks/CU — these
-    // shapes are HBM/L3-streaming-bound (MFMA <10% busy), so occupancy
-    // and independent load streams beat tile efficiency
-    // measured small-tile winners besides the 1x1s: the stem paths and
-    // shallow-K 3x3s at moderate M (deep-K 3x3s and the giant-M VGG
-    // b1.c2 regress -2..-20% at BM64 — B-tile re-staging doubles)
-    const bool small_conv =
-        stem_mode || (!one1 && (p.K <= 128 ||
-                                (p.K <= 576 && p.M <= 450000)));
-    const bool smallgemm =
-        (force_small || (!legacy && ((one1 && !wide) || small_conv))) &&
-        (long)((p.M + 63) / 64) * ((p.Cout + 63) / 64) >= 768;
-    // NOTE: a BM=256 x BN=128 512-thread 1-block/CU config was measured
-    // for the big-M deep-K 3x3s (to halve B re-staging: the BM128 D2
-    // config demands ~117 B/cyc/CU of L2 tile traffic vs ~56 available)
-    // and lost 10-24% — one resident block loses the cross-block
-    // epilogue/prologue overlap that two independent blocks provide.
-    const bool big = false;
-    if (smallgemm) {
-        BNsel = 64;
-        BMsel = 64;
-    } else if (wide) {
-        BNsel = 128;
-        BMsel = (mt128 * (p.Cout / 128) >= 384) ? 128 : 64;
-    } else {
-        BNsel = 64;
-        BMsel = (mt128 * ((p.Cout + 63) / 64) >= 384) ? 128 : 64;
-    }
-    // underfill guard: 256 CUs want >=256 workgroups; narrow the n-tile
-    // before leaving CUs idle (small-M deep-K shapes, e.g. 7x7x512)
-    if (BNsel == 128 &&
-        (long)((p.M + BMsel - 1) / BMsel) * ((p.Cout + 127) / 128) < 256) {
-        BNsel = 64;
-        BMsel = 64;
-    }
-    const int mtiles = (p.M + BMsel - 1) / BMsel;
-    const int ny = (p.Cout + BNsel - 1) / BNsel;
-    int gx = mtiles;
-    const int target = smallgemm ? (bp ? 1536 : 1152) : 768;
-    if ((long)mtiles * ny > target) {
-        gx = target / ny > 0 ? target / ny : 1;
-        if (gx > mtiles) gx = mtiles;
-    }
-    dim3 grid(gx, ny);
-    dim3 block(NTHREADS);
-    (void)big;   // see the BM256 note above
-
-#define DISPATCH_TILE(A, R, G, BP, BMv, BNv, D...)                        \
-    hipLaunchKernelGGL(                                                   \
-        (conv_igemm_kernel<A, R, G, BP, BMv, BNv, D>), grid, block, 0, s, \
-        p)
-#define DISPATCH_BOOLS(BMv, BNv, D...)                                    \
-    do {                                                                  \
-        if (relu) {                                                       \
-            if (has_res) {                                                \
-                if (amode == AMODE_GEMM) {                                \
-                    if (bp) DISPATCH_TILE(ACT_RELU, true, AMODE_GEMM,     \
-                                          true, BMv, BNv, D);             \
-                    else DISPATCH_TILE(ACT_RELU, true, AMODE_GEMM,        \
-                                       false, BMv, BNv, D);               \
-                } else if (amode == AMODE_RSC) {                          \
-                    DISPATCH_TILE(ACT_RELU, true, AMODE_RSC, false, BMv,  \
-                                  BNv, D);                                \
-                } else if (amode == AMODE_STEM) {                       \
-                    DISPATCH_TILE(ACT_RELU, true, AMODE_STEM, false,     \
-                                  BMv, BNv, D);                       \
-                } else {                                                  \
-                    if (bp) DISPATCH_TILE(ACT_RELU, true, AMODE_CONV,     \
-                                          true, BMv, BNv, D);             \
-                    else DISPATCH_TILE(ACT_RELU, true, AMODE_CONV,       \
-                                       false, BMv, BNv, D);               \
-                }                                                         \
-            } else {                                                      \
-                if (amode == AMODE_GEMM) {                                \
-                    if (bp) DISPATCH_TILE(ACT_RELU, false, AMODE_GEMM,    \
-                                          true, BMv, BNv, D);             \
-                    else DISPATCH_TILE(ACT_RELU, false, AMODE_GEMM,       \
-                                       false, BMv, BNv, D);               \
-                } else if (amode == AMODE_RSC) {                          \
-                    DISPATCH_TILE(ACT_RELU, false, AMODE_RSC, false,      \
-                                  BMv, BNv, D);                           \
-                } else if (amode == AMODE_STEM) {                       \
-                    DISPATCH_TILE(ACT_RELU, false, AMODE_STEM, false,     \
-                                  BMv, BNv, D);                       \
-                } else {                                                  \
-                    if (bp) DISPATCH_TILE(ACT_RELU, false, AMODE_CONV,    \
-                                          true, BMv, BNv, D);             \
-                    else DISPATCH_TILE(ACT_RELU, false, AMODE_CONV,       \
-                                       false, BMv, BNv, D);               \
-                }                                                         \
-            }                                                             \
-        } else {                                                          \
-            if (has_res) {                                                \
-                if (amode == AMODE_GEMM) {                                \
-                    if (bp) DISPATCH_TILE(ACT_NONE, true, AMODE_GEMM,     \
-                                          true, BMv, BNv, D);             \
-                    else DISPATCH_TILE(ACT_NONE, true, AMODE_GEMM,        \
-                                       false, BMv, BNv, D);               \
-                } else if (amode == AMODE_RSC) {                          \
-                    DISPATCH_TILE(ACT_NONE, true, AMODE_RSC, false, BMv,  \
-                                  BNv, D);                                \
-                } else if (amode == AMODE_STEM) {                       \
-                    DISPATCH_TILE(ACT_NONE, true, AMODE_STEM, false,     \
-                                  BMv, BNv, D);                       \
-                } else {                                                  \
-                    if (bp) DISPATCH_TILE(ACT_NONE, true, AMODE_CONV,     \
-                                          true, BMv, BNv, D);             \
-                    else DISPATCH_TILE(ACT_NONE, true, AMODE_CONV,        \
-                                       false, BMv, BNv, D);               \
-                }                                                         \
-            } else {                                                      \
-                if (amode == AMODE_GEMM) {                                \
-                    if (bp) DISPATCH_TILE(ACT_NONE, false, AMODE_GEMM,    \
-                                          true, BMv, BNv, D);             \
-                    else DISPATCH_TILE(ACT_NONE, false, AMODE_GEMM,       \
-                                       false, BMv, BNv, D);               \
-                } else if (amode == AMODE_RSC) {                          \
-                    DISPATCH_TILE(ACT_NONE, false, AMODE_RSC, false,      \
-                                  BMv, BNv, D);                           \
-                } else if (amode == AMODE_STEM) {                       \
-                    DISPATCH_TILE(ACT_NONE, false, AMODE_STEM, false,     \
-                                  BMv, BNv, D);                       \
-                } else {                                                  \
-                    if (bp) DISPATCH_TILE(ACT_NONE, false, AMODE_CONV,    \
-                                          true, BMv, BNv, D);             \
-                    else DISPATCH_TILE(ACT_NONE, false, AMODE_CONV,       \
-                                       false, BMv, BNv, D);               \
-                }                                                         \
-            }                                                             \
-        }                                                                 \
-    } while (0)
-
-    // depths (A-ring, B-ring). Measured on MI355X: symmetric depths win
-    // (boundary activations are L3/L2-resident, so one to two compute
-    // phases already cover the load latency and extra LDS per block
-    // costs more than deeper cover buys); the asymmetric deep-A variants
-    // (DEFER_CONV_VARIANT unset ... kept instantiated) lost 6-22% and
-    // remain only for the B_PERSIST single-K-tile shapes where a 4-deep
-    // A ring measured neutral-to-slightly-better.
-    if (BMsel == 128 && BNsel == 64) {
-        if (bp && !legacy) DISPATCH_BOOLS(128, 64, 4, 2);
-        else DISPATCH_BOOLS(128, 64, 3, 3);
-    } else if (BMsel == 128 && BNsel == 128) {
-        DISPATCH_BOOLS(128, 128, 2, 2);
-    } else if (BMsel == 64 && BNsel == 128) {
-        DISPATCH_BOOLS(64, 128, 3, 3);
-    } else if (smallgemm) {
-        if (bp) DISPATCH_BOOLS(64, 64, 4, 2, 4);   // 40 KB LDS, 4 blk/CU
-        else DISPATCH_BOOLS(64, 64, 3, 3, 3);      // 48 KB LDS, 3 blk/CU
-    } else {
-        if (bp && !legacy) DISPATCH_BOOLS(64, 64, 4, 2);
-        else DISPATCH_BOOLS(64, 64, 3, 3);
-    }
-#undef DISPATCH_BOOLS
-#undef DISPATCH_TILE
+    if (pl.family != ConvPlan::IGEMM)
+        p.smul = pl.full_sync ? 1u : 0u;   // full-sync debug flag
+    hipLaunchKernelGGL(find_row(pl).kernel[relu][has_res],
+                       dim3(pl.grid_x, pl.grid_y), dim3(NTHREADS), 0, s, p);
 }
 
 static int grid1d(long work, int block) {
@@ -1542,36 +1356,6 @@ void launch_swin_repack_w(const void* w, void* wp, int Cout, int R,
                        dim3(grid1d((long)Cout * Kpad, 256)), dim3(256),
                        0, s, (const bf16*)w, (bf16*)wp, Cout, R, C,
                        Kpad);
-}
-
-bool launch_conv_swin(const ConvParams& p0, bool relu, int R, int stride,
-                      hipStream_t s) {
-    // small-Cin window path: Cin padded to 8, Cout 64, R in {3,7},
-    // stride in {1,2}, 8x16 output tiles with <=18% padding waste
-    ConvParams p = p0;
-    // R==7 was implemented and dropped: the run-packed spatial-prepad
-    // stem path (K=168) beats the zero-padded window K=448 at Cin=3
-    if (p.Cout != 64 || R != 3 || !(stride == 1 || stride == 2))
-        return false;
-    long nth = (p.OH + 7) / 8, ntw = (p.OW + 15) / 16;
-    if (nth * 8 * ntw * 16 * 100 > (long)p.OH * p.OW * 118) return false;
-    long mt2 = (long)p.NB * nth * ntw;
-    static const char* fe = getenv("DEFER_CONV_VARIANT");
-    const bool forced = fe && (fe[0] == 'w' || fe[0] == 'W');
-    if (!forced && mt2 < 512) return false;
-    int gx = mt2 > 768 ? 768 : (int)mt2;
-    p.smul = 0;
-    dim3 grid(gx, 1), block(NTHREADS);
-#define SWIN(A, Rv, Sv)                                                       hipLaunchKernelGGL((conv_swin_kernel<A, Rv, Sv>), grid, block, 0, s,                        p)
-    if (stride == 2) {
-        if (relu) SWIN(ACT_RELU, 3, 2);
-        else SWIN(ACT_NONE, 3, 2);
-    } else {
-        if (relu) SWIN(ACT_RELU, 3, 1);
-        else SWIN(ACT_NONE, 3, 1);
-    }
-#undef SWIN
-    return true;
 }
 
 void launch_stem_repack_w(const void* w, void* wp, int Cout, int R, int S,

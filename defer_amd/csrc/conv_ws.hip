@@ -38,6 +38,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "conv_plan.h"
 #include "kernels.h"
 
 using defer_hip::ConvParams;
@@ -52,8 +53,6 @@ using defer_hip::ConvParams;
 #define WS_WCH (WS_WH * WS_ROW)     // chunks per window (24,320 B)
 #define WS_NSL ((WS_WCH + WS_TPB - 1) / WS_TPB)   // glds slices per wave
 #define WS_K (9 * 64)
-// policy threshold in output tiles (docs/OPTIMIZATION_LOG.md, round 6)
-#define WS_POLICY_MIN_TILES 512
 
 __device__ __forceinline__ void ws_glds16(const bf16* src, bf16* lds_base) {
     __builtin_amdgcn_global_load_lds(
@@ -306,56 +305,21 @@ __global__ __launch_bounds__(WS_TPB, 2) void conv_ws_kernel(ConvParams p) {
 
 namespace defer_hip {
 
-bool conv_ws_supported(const ConvParams& p) {
-    // element offsets inside one image are 32-bit in the kernel
-    return p.R == 3 && p.S == 3 && p.stride == 1 && p.pad == 1 &&
-           p.Cin == 64 && p.Cout == 64 && p.K == WS_K && p.NB >= 1 &&
-           p.H >= 1 && p.W >= 1 && p.OH == p.H && p.OW == p.W &&
-           (long)p.H * p.W < (1L << 24) &&
-           (long)p.NB * p.OH * p.OW < (1LL << 31);
-}
-
-static long ws_tiles(const ConvParams& p) {
-    return (long)p.NB * ((p.OH + WS_TH - 1) / WS_TH) *
-           ((p.OW + WS_TW - 1) / WS_TW);
-}
-
-bool conv_ws_policy(const ConvParams& p) {
-    // a forced DEFER_CONV_VARIANT is there to exercise the older kernels
-    static const bool variant = [] {
-        const char* e = getenv("DEFER_CONV_VARIANT");
-        return e && e[0];
-    }();
-    if (variant || !conv_ws_supported(p)) return false;
-    return ws_tiles(p) >= WS_POLICY_MIN_TILES;
-}
-
 ConvWsLaunch launch_conv_ws(const ConvParams& p, bool relu, bool has_res,
                             int max_blocks, hipStream_t s) {
-    // 2 blocks fit a CU, 512 on the chip; spread the rounds evenly over
-    // the blocks (7168 tiles: 512 blocks x 14)
-    const long tiles = ws_tiles(p);
-    long gx = max_blocks > 0 ? max_blocks : 512;
-    if (gx > tiles) gx = tiles;
-    const long rounds = (tiles + gx - 1) / gx;
-    gx = (tiles + rounds - 1) / rounds;
-    dim3 grid((unsigned)gx), block(WS_TPB);
-    if (relu) {
-        if (has_res)
-            hipLaunchKernelGGL((conv_ws_kernel<ACT_RELU, true>), grid, block,
-                               0, s, p);
-        else
-            hipLaunchKernelGGL((conv_ws_kernel<ACT_RELU, false>), grid,
-                               block, 0, s, p);
-    } else {
-        if (has_res)
-            hipLaunchKernelGGL((conv_ws_kernel<ACT_NONE, true>), grid, block,
-                               0, s, p);
-        else
-            hipLaunchKernelGGL((conv_ws_kernel<ACT_NONE, false>), grid,
-                               block, 0, s, p);
-    }
-    return ConvWsLaunch{(int)gx, (int)rounds};
+    static_assert(WS_TH == 8 && WS_TW == WIN_TW && WS_K == 9 * CONV_BK,
+                  "conv_plan.h plans 8x16 tiles");
+    // mode 1: the caller has chosen this kernel; the plan is its grid
+    const ConvPlan pl = plan_conv(p, false, false, 1, max_blocks, '\0');
+    if (pl.family != ConvPlan::WS)
+        throw std::runtime_error("no kernel for this plan: " +
+                                 to_string(pl));
+    static void (*const kernel[2][2])(ConvParams) = {
+        {conv_ws_kernel<ACT_NONE, false>, conv_ws_kernel<ACT_NONE, true>},
+        {conv_ws_kernel<ACT_RELU, false>, conv_ws_kernel<ACT_RELU, true>}};
+    hipLaunchKernelGGL(kernel[relu][has_res], dim3(pl.blocks),
+                       dim3(WS_TPB), 0, s, p);
+    return ConvWsLaunch{pl.blocks, pl.tiles_per_block};
 }
 
 }  // namespace defer_hip

@@ -1,5 +1,6 @@
 // Host-visible launcher API for the defer_amd gfx950 kernel library.
-// Implemented in the .hip TUs; called from the torch bindings.
+// Implemented in the .hip TUs; called from the torch bindings. The bf16
+// conv launchers and their kernel selection are in conv_plan.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -21,45 +22,20 @@ struct ConvParams {
     // magic-multiply reciprocals (filled by launch_conv_igemm):
     // floor(n/d) = umulhi(n, ceil(2^32/d)) for n*d < 2^32.
     // The window kernels do not divide; they reuse `smul` as a
-    // full-sync debug flag (DEFER_CONV_VARIANT=W forces vmcnt(0)
-    // drains every phase).
+    // full-sync debug flag (ConvPlan::full_sync, DEFER_CONV_VARIANT=W,
+    // forces vmcnt(0) drains every phase).
     unsigned int owmul, ohmul, cmul, smul;
 };
 
-void launch_conv_igemm(const ConvParams& p, bool relu, bool has_res,
-                       bool gemm_mode, bool stem_mode, hipStream_t s);
 void launch_pad_channels(const void* x, void* y, long rows, int C, int C8,
                          hipStream_t s);
 // STEM path helpers: spatial zero-pad + weight repack to (r, run) K-order
 void launch_pad2d(const void* x, void* y, int NB, int H, int W, int C,
                   int PH, int PW, int ph0, int pw0, hipStream_t s);
-// small-Cin window stem path (R in {3,7}, stride in {1,2}, Cout 64,
-// Cin pre-padded to 8; weights pre-repacked j-major zero-padded).
-// Returns false if the shape does not qualify (caller falls back).
-bool launch_conv_swin(const ConvParams& p, bool relu, int R, int stride,
-                      hipStream_t s);
 void launch_swin_repack_w(const void* w, void* wp, int Cout, int R,
                           int C, int Kpad, hipStream_t s);
 void launch_stem_repack_w(const void* w, void* wp, int Cout, int R, int S,
                           int C, int TR, hipStream_t s);
-
-// weight-stationary window kernel (conv_ws.hip): 3x3/s1/p1 convs with
-// Cin = Cout = 64 keep the whole weight tensor in registers and stage only
-// input windows to LDS; bit-identical to launch_conv_igemm on the same
-// ConvParams (relu or none, with or without residual).
-// conv_ws_supported: the kernel covers this geometry. conv_ws_policy: it
-// also measured faster than the paths of launch_conv_igemm for this shape
-// class (never when DEFER_CONV_VARIANT forces one of those).
-bool conv_ws_supported(const ConvParams& p);
-bool conv_ws_policy(const ConvParams& p);
-struct ConvWsLaunch {
-    int blocks;            // grid size
-    int tiles_per_block;   // 8x16 output tiles the busiest block walks
-};
-// max_blocks caps the grid (0 = the 512 resident blocks) so a few blocks
-// walk many tiles.
-ConvWsLaunch launch_conv_ws(const ConvParams& p, bool relu, bool has_res,
-                            int max_blocks, hipStream_t s);
 
 // fused pre-activation 1x1 conv: out = relu(x*ps+pb) @ w^T
 // (DenseNet BNActConv; bit-identical to bn_act -> conv GEMM mode)

@@ -59,16 +59,35 @@ def _backend(x: torch.Tensor):
     return None
 
 
+_MODES = {None: 0, "": 0, "force": 1, "0": 2}
+
+
+def _env_mode(name):
+    """The 0/1/2 mode that the A/B switch `name` asks for (read at import)."""
+    value = os.environ.get(name)
+    if value not in _MODES:
+        raise ValueError(
+            f"{name}={value!r}: expected unset, '0' or 'force'")
+    return _MODES[value]
+
+
+def _built():
+    m = _load_hip()
+    if m is None:
+        raise RuntimeError(
+            f"defer_amd HIP extension is not built: {_hip_err!r}")
+    return m
+
+
+def _stats(name):
+    return dict(getattr(_built(), name)())
+
+
 # A/B switch for the weight-stationary 3x3 kernel (same convention as
 # DEFER_CONV_CHAIN): unset = the launcher's measured policy, "0" = always
 # the older conv paths, "force" = the new kernel wherever it covers the
 # shape.
-_CONV_WS_MODES = {None: 0, "": 0, "force": 1, "0": 2}
-_conv_ws_env = os.environ.get("DEFER_CONV_WS")
-if _conv_ws_env not in _CONV_WS_MODES:
-    raise ValueError(
-        f"DEFER_CONV_WS={_conv_ws_env!r}: expected unset, '0' or 'force'")
-_CONV_WS_MODE = _CONV_WS_MODES[_conv_ws_env]
+_CONV_WS_MODE = _env_mode("DEFER_CONV_WS")
 
 
 def conv2d_bn_act(x, w, scale=None, bias=None, stride=1, padding=1,
@@ -91,16 +110,25 @@ def conv2d_bn_act(x, w, scale=None, bias=None, stride=1, padding=1,
                            max_blocks)
 
 
+def conv_plan(x_shape, w_shape, stride=1, padding=1, residual=False,
+              mode=None, max_blocks=0, variant=None):
+    """What conv2d_bn_act (NHWC / OHWI shapes) or linear (2-D shapes) would
+    launch on the GPU for bf16 tensors of these shapes, without launching
+    it: {"path", "family", the tile config or window height, "grid_x",
+    "grid_y", "template_args", ...}. Needs the built extension but no GPU.
+    mode as in conv2d_bn_act; variant: a DEFER_CONV_VARIANT value, None =
+    the environment's."""
+    return dict(_built().conv_plan(
+        list(x_shape), list(w_shape), stride, padding, bool(residual),
+        _CONV_WS_MODE if mode is None else mode, max_blocks, variant))
+
+
 def conv_ws_stats():
     """What the weight-stationary 3x3 path of conv2d_bn_act did in this
     process: {"launches": kernel launches so far, "blocks",
     "tiles_per_block": the grid of the last one}. Lets tests tell the new
     kernel from the older paths, whose results are identical by design."""
-    m = _load_hip()
-    if m is None:
-        raise RuntimeError(
-            f"defer_amd HIP extension is not built: {_hip_err!r}")
-    return dict(m.conv_ws_stats())
+    return _stats("conv_ws_stats")
 
 
 def conv1x1_prebn(x, w, scale, bias, out_scale=None, out_bias=None):
@@ -128,12 +156,7 @@ def conv1x1_prebn(x, w, scale, bias, out_scale=None, out_bias=None):
 # A/B switch for the chained expand->reduce kernel (mirrors
 # DEFER_CONV_VARIANT): unset = the launcher's measured policy, "0" = always
 # two launches, "force" = fused wherever an instantiation exists.
-_CHAIN_MODES = {None: 0, "": 0, "force": 1, "0": 2}
-_chain_env = os.environ.get("DEFER_CONV_CHAIN")
-if _chain_env not in _CHAIN_MODES:
-    raise ValueError(
-        f"DEFER_CONV_CHAIN={_chain_env!r}: expected unset, '0' or 'force'")
-_CHAIN_MODE = _CHAIN_MODES[_chain_env]
+_CHAIN_MODE = _env_mode("DEFER_CONV_CHAIN")
 
 
 def conv1x1_chain(x, w3, s3, b3, residual, act3, w1, s1, b1, act1,
@@ -165,13 +188,7 @@ def conv1x1_chain(x, w3, s3, b3, residual, act3, w1, s1, b1, act1,
 # (same convention as DEFER_CONV_CHAIN): unset = the launcher's measured
 # policy, "0" = always the projection launch plus conv1x1_chain, "force" =
 # the kernel wherever it serves the shape.
-_CHAIN_PROJ_MODES = {None: 0, "": 0, "force": 1, "0": 2}
-_chain_proj_env = os.environ.get("DEFER_CHAIN_PROJ")
-if _chain_proj_env not in _CHAIN_PROJ_MODES:
-    raise ValueError(
-        f"DEFER_CHAIN_PROJ={_chain_proj_env!r}: expected unset, '0' or "
-        f"'force'")
-_CHAIN_PROJ_MODE = _CHAIN_PROJ_MODES[_chain_proj_env]
+_CHAIN_PROJ_MODE = _env_mode("DEFER_CHAIN_PROJ")
 
 
 def conv1x1_chain_proj(x, w3, s3, b3, xp, wp, sp, bp, act3, w1, s1, b1,
@@ -210,22 +227,13 @@ def chain_proj_stats():
     of the projected-residual kernel so far, "blocks": the grid of the last
     one}. Lets tests tell that kernel from the composed ops, whose results
     are identical by design."""
-    m = _load_hip()
-    if m is None:
-        raise RuntimeError(
-            f"defer_amd HIP extension is not built: {_hip_err!r}")
-    return dict(m.chain_proj_stats())
+    return _stats("chain_proj_stats")
 
 
 # A/B switch for the fused stem conv + max-pool kernel (same convention as
 # DEFER_CONV_CHAIN): unset = the binding's policy, "0" = always two
 # launches, "force" = fused wherever the kernel covers the shape.
-_STEM_POOL_MODES = {None: 0, "": 0, "force": 1, "0": 2}
-_stem_pool_env = os.environ.get("DEFER_STEM_POOL")
-if _stem_pool_env not in _STEM_POOL_MODES:
-    raise ValueError(
-        f"DEFER_STEM_POOL={_stem_pool_env!r}: expected unset, '0' or 'force'")
-_STEM_POOL_MODE = _STEM_POOL_MODES[_stem_pool_env]
+_STEM_POOL_MODE = _env_mode("DEFER_STEM_POOL")
 
 
 def conv_bn_act_maxpool(x, w, scale, bias, stride, padding, act,
@@ -258,11 +266,7 @@ def stem_pool_stats():
     {"launches": fused-kernel launches so far, "bands", "rows_per_band":
     the band split of the last one}. Lets tests tell the fused kernel from
     the two launches, whose results are identical by design."""
-    m = _load_hip()
-    if m is None:
-        raise RuntimeError(
-            f"defer_amd HIP extension is not built: {_hip_err!r}")
-    return dict(m.stem_pool_stats())
+    return _stats("stem_pool_stats")
 
 
 def batchnorm_apply(x, scale, bias, act="none"):
