@@ -40,12 +40,17 @@ class PipelineConfig:
     # Codec for boundary activations. The reference compresses with
     # lz4(zfp(x)) (dispatcher.py:81-84). "none" ships raw bf16 over xGMI;
     # "fp8" ships a cast-only e4m3 wire (1 B/value, ~free); "zfp" ships
-    # fixed-rate ZFP blocks; "zfp+lz4" adds the LZ4 stage.
+    # fixed-rate ZFP blocks; "zfp+lz4" adds the LZ4 stage. Those three
+    # are lossy. "lossless" packs the bit patterns (zero mask + exponent
+    # offsets, ops/pack_ref.py) for bf16 and fp32: fewer bytes and
+    # bit-identical results, which is what the reference's wire gives
+    # (zfpy.compress_numpy without a rate is ZFP's reversible mode).
     # "auto" picks the wire PER HOP: fp8 on hops whose raw-bf16 relay
     # would exceed the slowest stage's compute (the pipeline bottleneck),
     # lossless bf16 elsewhere (comm.choose_hop_modes — deterministic
     # from the calibration + cuts, so all ranks agree).
-    compression: str = "none"  # "none"|"fp8"|"zfp"|"zfp+lz4"|"auto"
+    # "none"|"fp8"|"zfp"|"zfp+lz4"|"lossless"|"auto"
+    compression: str = "none"
     zfp_rate_bits: int = 8        # fixed-rate bits per value (ZFP)
 
     # Depth of the per-stage device-resident activation ring buffers (the
@@ -60,7 +65,8 @@ class PipelineConfig:
     # bandwidth for the early fat boundaries that exceed one 153 GB/s
     # link (ResNet50 layer1: 1.6 MB/img = 10.5 us/hop, the 8-stage
     # bottleneck — profiles/README.md "Predicted pipeline scaling").
-    # Requires world > 2 and a fixed-size wire (not "zfp+lz4").
+    # Requires world > 2 and a fixed-size wire: both variable-size wires
+    # ("zfp+lz4" and "lossless") are excluded.
     # bench.py defaults it ON at world >= 4 (with a warmup stall
     # watchdog that re-execs single-rail, since the first RCCL
     # execution is the round-end multi-GPU run itself); the raw
@@ -99,10 +105,10 @@ class PipelineConfig:
 
     def __post_init__(self):
         if self.compression not in ("none", "fp8", "zfp", "zfp+lz4",
-                                    "auto"):
+                                    "lossless", "auto"):
             raise ValueError(
                 f"unknown compression {self.compression!r} "
-                "(none|fp8|zfp|zfp+lz4|auto)")
+                "(none|fp8|zfp|zfp+lz4|lossless|auto)")
         if self.dtype not in ("bf16", "fp16", "fp32"):
             raise ValueError(f"unknown dtype {self.dtype!r} "
                              "(bf16|fp16|fp32)")

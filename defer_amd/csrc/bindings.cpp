@@ -1127,6 +1127,80 @@ Tensor lz4_decompress(Tensor comp, int64_t raw_len) {
     return o;
 }
 
+// ---- lossless wire (csrc/pack.hip, spec in ops/pack_ref.py) ----
+static int pack_elem_bits(const Tensor& x) {
+    TORCH_CHECK(x.scalar_type() == at::kBFloat16
+                || x.scalar_type() == at::kFloat,
+                "lossless wire packs bf16 or fp32, got ", x.scalar_type());
+    return x.scalar_type() == at::kBFloat16 ? 16 : 32;
+}
+
+static void pack_check_numel(long n, int bits) {
+    TORCH_CHECK(n > 0, "empty input");
+    // chunk_off[] holds u32 word offsets into the payload
+    TORCH_CHECK(defer_hip::pack_wire_bytes_max(n, bits) / 4 < (1ll << 32),
+                "tensor too large for the lossless wire's u32 offsets");
+}
+
+// Fully async lossless hop encode: pack `x` into the caller's worst-case
+// `out` ring slot and write the exact wire byte count into `len_out`
+// (device int64) — the same contract as lz4_compress_into. Bytes of
+// `out` past the wire are left untouched.
+void pack_encode_into(Tensor x, Tensor scratch, Tensor out,
+                      Tensor len_out) {
+    TORCH_CHECK(x.is_cuda() && x.is_contiguous(), "x must be GPU contig");
+    int bits = pack_elem_bits(x);
+    long n = x.numel();
+    pack_check_numel(n, bits);
+    TORCH_CHECK(scratch.is_cuda() && scratch.is_contiguous()
+                && scratch.scalar_type() == at::kByte
+                && scratch.numel() >= defer_hip::pack_scratch_bytes(n, bits)
+                && (uintptr_t)scratch.data_ptr() % 4 == 0,
+                "scratch too small or misaligned");
+    TORCH_CHECK(out.is_cuda() && out.is_contiguous()
+                && out.scalar_type() == at::kByte
+                && out.numel() >= defer_hip::pack_wire_bytes_max(n, bits)
+                && (uintptr_t)out.data_ptr() % 4 == 0,
+                "out too small or misaligned");
+    TORCH_CHECK(len_out.is_cuda() && len_out.numel() == 1
+                && len_out.scalar_type() == at::kLong, "bad len_out");
+    defer_hip::launch_pack_encode(bptr(x), n, bits == 16,
+                                  bptr_mut(scratch), bptr_mut(out),
+                                  bptr_mut(len_out), cur_stream());
+}
+
+// convenience form: exact-size wire (syncs the stream to read the size)
+Tensor pack_encode(Tensor x) {
+    TORCH_CHECK(x.is_cuda() && x.is_contiguous(), "x must be GPU contig");
+    int bits = pack_elem_bits(x);
+    long n = x.numel();
+    pack_check_numel(n, bits);
+    auto bopt = x.options().dtype(at::kByte);
+    auto scratch = at::empty({defer_hip::pack_scratch_bytes(n, bits)}, bopt);
+    auto o = at::empty({defer_hip::pack_wire_bytes_max(n, bits)}, bopt);
+    auto len = at::empty({1}, x.options().dtype(at::kLong));
+    defer_hip::launch_pack_encode(bptr(x), n, bits == 16,
+                                  bptr_mut(scratch), bptr_mut(o),
+                                  bptr_mut(len), cur_stream());
+    long total = len.item<int64_t>();
+    return o.narrow(0, 0, total);
+}
+
+Tensor pack_decode(Tensor wire, std::vector<int64_t> shape, bool bf16_out) {
+    TORCH_CHECK(wire.is_cuda() && wire.is_contiguous()
+                && wire.scalar_type() == at::kByte
+                && (uintptr_t)wire.data_ptr() % 4 == 0, "bad wire");
+    auto y = at::empty(shape, wire.options().dtype(
+                                  bf16_out ? at::kBFloat16 : at::kFloat));
+    long n = y.numel();
+    pack_check_numel(n, bf16_out ? 16 : 32);
+    TORCH_CHECK(wire.numel() >= defer_hip::pack_table_bytes(n),
+                "wire shorter than its tables for this shape");
+    defer_hip::launch_pack_decode(bptr(wire), wire.numel(), bptr_mut(y), n,
+                                  bf16_out, cur_stream());
+    return y;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1180,4 +1254,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("lz4_scratch_bytes",
           [](int64_t n) { return defer_hip::lz4_scratch_bytes(n); });
     m.def("lz4_decompress", &lz4_decompress);
+    m.def("pack_scratch_bytes", [](int64_t n, int64_t bits) {
+        return defer_hip::pack_scratch_bytes(n, (int)bits);
+    });
+    m.def("pack_wire_bytes_max", [](int64_t n, int64_t bits) {
+        return defer_hip::pack_wire_bytes_max(n, (int)bits);
+    });
+    m.def("pack_encode_into", &pack_encode_into);
+    m.def("pack_encode", &pack_encode);
+    m.def("pack_decode", &pack_decode);
 }

@@ -187,4 +187,19 @@ void launch_lz4_wire_len(const void* out_stream, long n, void* len_out,
 void launch_lz4_decompress(const void* comp, void* out, long raw_len,
                            hipStream_t s);
 
+// lossless zero-mask + exponent-offset wire (see csrc/pack.hip /
+// ops/pack_ref.py); elem_bits = 16 (bf16) or 32 (fp32)
+long pack_table_bytes(long numel);   // header + chunk_off[] + len[]
+long pack_wire_bytes_max(long numel, int elem_bits);
+long pack_scratch_bytes(long numel, int elem_bits);
+// encodes numel values of x into `out` (>= pack_wire_bytes_max bytes,
+// 4-byte aligned) and writes the exact wire byte count into *size_out
+// (device int64, may be null); async, no host sync
+void launch_pack_encode(const void* x, long numel, bool bf16_in,
+                        void* scratch, void* out, void* size_out,
+                        hipStream_t s);
+// wire_bytes bounds the reads: records past it decode to zeros
+void launch_pack_decode(const void* wire, long wire_bytes, void* y,
+                        long numel, bool bf16_out, hipStream_t s);
+
 }  // namespace defer_hip

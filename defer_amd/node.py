@@ -37,7 +37,8 @@ def main():
     ap.add_argument("--report", type=int, default=64,
                     help="rank 0 prints throughput every N items")
     ap.add_argument("--compression", default="none",
-                    choices=["none", "fp8", "zfp", "zfp+lz4", "auto"])
+                    choices=["none", "fp8", "zfp", "zfp+lz4", "lossless",
+                             "auto"])
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"])
     ap.add_argument("--dtype", default=None, choices=["bf16", "fp32"],
                     help="compute dtype (default: bf16 on cuda, fp32 on "

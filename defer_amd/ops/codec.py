@@ -1,6 +1,8 @@
-"""Activation codec ops: fixed-rate ZFP (GPU kernels; numpy reference on
-CPU). Wire format is fixed-size per tensor shape+rate, so pipeline recv
-buffers are preallocated rings (comm.py)."""
+"""Activation codec ops: fixed-rate ZFP, LZ4 and the lossless pack wire
+(GPU kernels; numpy references on CPU). The ZFP wire is fixed-size per
+tensor shape+rate, so pipeline recv buffers are preallocated rings
+(comm.py); LZ4 and pack outputs are data-dependent and ride the
+variable-size ring."""
 
 import numpy as np
 import torch
@@ -72,3 +74,65 @@ def zfp_decode(wire: torch.Tensor, shape, rate: int,
                             dtype == torch.bfloat16)
     a = zfp_ref.decode(wire.numpy(), tuple(shape), rate)
     return torch.from_numpy(a).to(dtype)
+
+
+# ---- lossless wire (csrc/pack.hip on GPU, ops/pack_ref.py on CPU) --------
+
+def _pack_bits(dtype) -> int:
+    if dtype == torch.bfloat16:
+        return 16
+    if dtype == torch.float32:
+        return 32
+    raise TypeError(
+        f"the lossless wire packs bf16 or fp32 tensors, got {dtype}")
+
+
+def pack_wire_bytes_max(shape, dtype) -> int:
+    """Worst-case lossless wire size for a tensor of this shape/dtype."""
+    from defer_amd.ops import pack_ref
+
+    numel = 1
+    for d in tuple(shape):
+        numel *= int(d)
+    return pack_ref.wire_bytes_max(numel, _pack_bits(dtype))
+
+
+def pack_encode(x: torch.Tensor) -> torch.Tensor:
+    """x: bf16 or fp32 tensor -> exact-size uint8 wire from which
+    pack_decode rebuilds every bit pattern."""
+    bits = _pack_bits(x.dtype)
+    if x.is_cuda:
+        from defer_amd import ops as _ops
+
+        m = _ops._load_hip()
+        if m is None:
+            raise RuntimeError("HIP extension missing for pack_encode")
+        return m.pack_encode(x.contiguous())
+    from defer_amd.ops import pack_ref
+
+    xc = x.detach().contiguous()
+    if bits == 16:
+        a = xc.view(torch.int16).numpy().view(np.uint16)
+    else:
+        a = xc.view(torch.int32).numpy().view(np.uint32)
+    return torch.from_numpy(pack_ref.encode(a))
+
+
+def pack_decode(wire: torch.Tensor, shape,
+                dtype=torch.bfloat16) -> torch.Tensor:
+    bits = _pack_bits(dtype)
+    if wire.is_cuda:
+        from defer_amd import ops as _ops
+
+        m = _ops._load_hip()
+        if m is None:
+            raise RuntimeError("HIP extension missing for pack_decode")
+        return m.pack_decode(wire.contiguous(), list(shape), bits == 16)
+    from defer_amd.ops import pack_ref
+
+    w = wire.contiguous().view(-1).numpy()
+    if bits == 16:
+        a = pack_ref.decode(w, tuple(shape), np.uint16)
+        return torch.from_numpy(a.view(np.int16).copy()).view(torch.bfloat16)
+    a = pack_ref.decode(w, tuple(shape), np.uint32)
+    return torch.from_numpy(a.view(np.int32).copy()).view(torch.float32)

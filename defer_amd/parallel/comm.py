@@ -16,6 +16,10 @@ import torch.distributed as dist
 
 from defer_amd.config import PipelineConfig
 
+# wires whose size depends on the data: they ride VarP2PRing and are
+# excluded from dual-rail (which splits a fixed-size buffer)
+VARIABLE_MODES = ("zfp+lz4", "lossless")
+
 
 def choose_hop_modes(stage_us, hop_bytes, link_gbps, dual_boosts=None):
     """Per-hop wire mode for compression="auto": a hop whose raw-bf16
@@ -79,6 +83,20 @@ class Codec:
             self.wire_numel = 4 * (2 + nb + 1) + nb * 4352
             self.wire_dtype = torch.uint8
             self.variable = True
+        elif self.mode == "lossless":
+            # zero-mask + exponent-offset packing of the bit patterns
+            # (ops/pack_ref.py): the reference's default wire is also
+            # lossless (zfpy.compress_numpy with no rate is ZFP's
+            # reversible mode). Data-dependent size -> variable-size
+            # hop, buffers sized for the worst case (< 1.11x raw).
+            from defer_amd.ops import codec as zc
+            if dtype not in (torch.bfloat16, torch.float32):
+                raise ValueError(
+                    f"compression='lossless' packs bf16 or fp32 "
+                    f"activations, got {dtype}")
+            self.wire_numel = zc.pack_wire_bytes_max(self.shape, dtype)
+            self.wire_dtype = torch.uint8
+            self.variable = True
         else:
             raise ValueError(f"unknown compression {self.mode!r}")
 
@@ -112,9 +130,58 @@ class Codec:
             out[4:].copy_(q.view(torch.uint8).reshape(-1))
             return out
         from defer_amd.ops import codec as zc
+        if self.mode == "lossless":
+            if x.dtype != self.dtype:
+                raise ValueError(
+                    f"lossless codec built for {self.dtype}, got {x.dtype}")
+            return zc.pack_encode(x)
         if self.variable:
             return zc.lz4_compress(zc.zfp_encode(x, self.rate))
         return zc.zfp_encode(x, self.rate, out=out)
+
+    # -- variable-size hops on the GPU (VarP2PRing's CUDA sender): encode
+    # straight into a worst-case ring slot with the byte count left in a
+    # device int64, so the size message never visits the host
+    def alloc_hop_scratch(self):
+        """Device scratch that encode_into needs, allocated once per ring."""
+        from defer_amd import ops as _ops
+
+        m = _ops._load_hip()
+        if m is None:
+            raise RuntimeError(
+                f"HIP extension missing for {self.mode} hop")
+        if self.mode == "zfp+lz4":
+            zb = self.zfp_bytes
+            zfp_buf = torch.empty(zb, dtype=torch.uint8, device=self.device)
+            scratch = torch.empty(int(m.lz4_scratch_bytes(zb)),
+                                  dtype=torch.uint8, device=self.device)
+            return (zfp_buf, scratch)
+        if self.mode == "lossless":
+            numel = int(torch.tensor(self.shape).prod())
+            bits = 16 if self.dtype == torch.bfloat16 else 32
+            return torch.empty(int(m.pack_scratch_bytes(numel, bits)),
+                               dtype=torch.uint8, device=self.device)
+        raise ValueError(f"{self.mode!r} is not a variable-size wire")
+
+    def encode_into(self, x: torch.Tensor, slot: torch.Tensor,
+                    size: torch.Tensor, scratch):
+        """Async: wire of x -> slot[:n], n -> size (device int64)."""
+        from defer_amd import ops as _ops
+
+        m = _ops._load_hip()
+        if self.mode == "zfp+lz4":
+            from defer_amd.ops import codec as zc
+
+            zfp_buf, lz_scratch = scratch
+            zc.zfp_encode(x, self.rate, out=zfp_buf)
+            m.lz4_compress_into(zfp_buf, lz_scratch, slot, size)
+        elif self.mode == "lossless":
+            if x.dtype != self.dtype:
+                raise ValueError(
+                    f"lossless codec built for {self.dtype}, got {x.dtype}")
+            m.pack_encode_into(x.contiguous(), scratch, slot, size)
+        else:
+            raise ValueError(f"{self.mode!r} is not a variable-size wire")
 
     def decode(self, wire: torch.Tensor) -> torch.Tensor:
         if self.mode == "none":
@@ -134,6 +201,8 @@ class Codec:
             return (vals * scale).to(self.dtype) \
                 .view(self.shape)
         from defer_amd.ops import codec as zc
+        if self.mode == "lossless":
+            return zc.pack_decode(wire, self.shape, dtype=self.dtype)
         if self.variable:
             wire = zc.lz4_decompress(wire, self.zfp_bytes)
         return zc.zfp_decode(wire, self.shape, self.rate,
@@ -199,9 +268,11 @@ class P2PRing:
 
 
 class VarP2PRing(P2PRing):
-    """Variable-size hop (zfp+lz4): each item is an 8-byte size message
-    followed by the exact-size payload — the RCCL analogue of the
-    reference's length-prefixed TCP framing (node_state.py:44-54).
+    """Variable-size hop (zfp+lz4, lossless): each item is an 8-byte size
+    message followed by the exact-size payload — the RCCL analogue of the
+    reference's length-prefixed TCP framing (node_state.py:44-54). The
+    ring knows nothing about the wire format: the codec encodes an item
+    into a slot and a device size tensor (Codec.encode_into).
 
     RCCL and gloo match p2p ops strictly in issue order per (src,dst)
     pair (no tags), so BOTH sides follow one interleave for K items:
@@ -211,7 +282,7 @@ class VarP2PRing(P2PRing):
     (s_k = size of item k, p_k = its exact-size payload). The payload
     send of item k is deferred until item k+1's encode has been issued
     (or flush()): on RCCL the size message is sent straight from device
-    memory — lz4_compress_into writes the device int64, no host
+    memory — the encode's last kernel writes the device int64, no host
     round-trip — and the host reads a pinned copy one item later, so
     the sender's host loop never blocks on the codec kernels of the
     item it is currently issuing (the round-1 per-item .to(kCPU) sync
@@ -246,17 +317,8 @@ class VarP2PRing(P2PRing):
         self._dst: Optional[int] = None
         self._host_n = [0] * self.depth       # CPU path: size known now
         if self.cuda:
-            from defer_amd import ops as _ops
-
-            self._hip = _ops._load_hip()
-            if self._hip is None:
-                raise RuntimeError("HIP extension missing for zfp+lz4 hop")
-            zb = codec.zfp_bytes
-            self._zfp_buf = torch.empty(zb, dtype=torch.uint8,
-                                        device=codec.device)
-            self._scratch = torch.empty(
-                int(self._hip.lz4_scratch_bytes(zb)), dtype=torch.uint8,
-                device=codec.device)
+            # what the codec's device-side encode needs besides the slot
+            self._scratch = codec.alloc_hop_scratch()
             self._pinned = [torch.zeros(1, dtype=torch.long,
                                         pin_memory=True)
                             for _ in range(self.depth)]
@@ -299,11 +361,8 @@ class VarP2PRing(P2PRing):
         self.wait(k)                      # payload slot free (k-depth)
         self._wait_size(k)                # size slot free (k-depth)
         if self.cuda:
-            from defer_amd.ops import codec as zc
-
-            zc.zfp_encode(y, self.codec.rate, out=self._zfp_buf)
-            self._hip.lz4_compress_into(self._zfp_buf, self._scratch,
-                                        self.bufs[i], self.sizes[i])
+            self.codec.encode_into(y, self.bufs[i], self.sizes[i],
+                                   self._scratch)
             self.size_works[i] = dist.isend(self.sizes[i], dst=dst)
             self._pinned[i].copy_(self.sizes[i], non_blocking=True)
             self._events[i].record()
@@ -361,10 +420,10 @@ def split_point(numel: int) -> int:
 def dual_active(cfg: PipelineConfig, world: int) -> bool:
     """Single source of truth for whether dual-rail rings are built:
     needs a third rank to route through and a fixed-size wire (zfp+lz4
-    is variable-size). The partitioner's bandwidth credit
+    and lossless are variable-size). The partitioner's bandwidth credit
     (dual_bw_boost) derives from this so the two can't drift apart."""
     return bool(cfg.dual_rail) and world > 2 \
-        and cfg.compression != "zfp+lz4"
+        and cfg.compression not in VARIABLE_MODES
 
 
 def dual_bw_boost(cfg: PipelineConfig, world: int) -> float:

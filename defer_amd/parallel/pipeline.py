@@ -24,8 +24,9 @@ import torch.distributed as dist
 
 from defer_amd.config import PipelineConfig
 from defer_amd.graph import GraphModel
-from defer_amd.parallel.comm import (Codec, DualRailRing, HopForwarder,
-                                     P2PRing, dtype_bytes, dual_active,
+from defer_amd.parallel.comm import (VARIABLE_MODES, Codec, DualRailRing,
+                                     HopForwarder, P2PRing, dtype_bytes,
+                                     dual_active,
                                      dual_bw_boost, hop_via, make_ring,
                                      split_point)
 from defer_amd.parallel.partitioner import (as_graph_model, auto_partition,
@@ -376,8 +377,8 @@ class DistPipeline:
             import sys
 
             print("defer_amd: dual_rail ignored "
-                  + ("(variable-size zfp+lz4 wire)"
-                     if cfg.compression == "zfp+lz4"
+                  + (f"(variable-size {cfg.compression} wire)"
+                     if cfg.compression in VARIABLE_MODES
                      else "(needs world > 2)"), file=sys.stderr)
         if self.world > 1:
             # a wire too small to split (codec.wire_numel < 16) stays
@@ -488,6 +489,9 @@ class DistPipeline:
             return self.cfg.zfp_rate_bits / 8.0
         if self.cfg.compression == "fp8":
             return 1.0
+        # "lossless" lands here too: its hop size depends on the data
+        # (zeros, exponent spread), so the raw element size stands in as
+        # an upper bound up to the < 1.11x worst-case expansion
         return 2.0 if self.cfg.dtype == "bf16" else 4.0
 
     def _boundary_shapes(self, stages):
