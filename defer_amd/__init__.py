@@ -23,3 +23,4 @@ __version__ = "0.1.0"
 from defer_amd.config import PipelineConfig  # noqa: F401
 from defer_amd.parallel.pipeline import DEFER, DistPipeline  # noqa: F401
 from defer_amd.parallel.partitioner import partition_model, auto_partition  # noqa: F401
+from defer_amd.lower import lower_torch, lowering_report  # noqa: F401

@@ -23,6 +23,12 @@ class PipelineConfig:
     # (batch dim 1). Defaults to the reference workload's 224x224x3 NHWC
     # image (test/test.py:20) when None.
     input_shape: Optional[tuple] = None
+    # Lower a plain torch nn.Module onto the project's NHWC HIP layers
+    # (defer_amd.lower.lower_torch) instead of running its own layers in
+    # NCHW through PyTorch's kernels. Needs input_shape, the model's own
+    # NCHW input shape. Off by default; GraphModels and LayerGraphs are
+    # never touched.
+    lower: bool = False
 
     # --- execution --------------------------------------------------------
     device: str = "cuda"          # "cuda" (MI355X) or "cpu" (tests/plumbing)
@@ -112,6 +118,13 @@ class PipelineConfig:
         if self.dtype not in ("bf16", "fp16", "fp32"):
             raise ValueError(f"unknown dtype {self.dtype!r} "
                              "(bf16|fp16|fp32)")
+        if not isinstance(self.lower, bool):
+            raise ValueError(f"lower must be a bool, got {self.lower!r}")
+        if self.lower and (self.input_shape is None
+                           or len(tuple(self.input_shape)) != 4):
+            raise ValueError(
+                "lower=True needs input_shape, the model's NCHW input "
+                f"shape (4 dims), got {self.input_shape!r}")
         if self.ring_depth < 1:
             raise ValueError("ring_depth must be >= 1")
         if not 1 <= self.zfp_rate_bits <= 30:

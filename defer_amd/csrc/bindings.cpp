@@ -1003,6 +1003,41 @@ Tensor global_avg_pool(Tensor x) {
     return out;
 }
 
+// NCHW -> NHWC (to_nhwc) or back, converting between fp32 and bf16 on the
+// way when bf16_out differs from x's dtype. `out`, when given, is the
+// contiguous destination of the right shape and dtype (lets a caller own
+// the buffer); otherwise a fresh at::empty tensor. One launch on the
+// current stream, no sync, so it can be captured into a hipGraph.
+Tensor layout_convert(Tensor x, bool to_nhwc, bool bf16_out,
+                      c10::optional<Tensor> out) {
+    TORCH_CHECK(x.is_cuda(), "x must be on GPU");
+    const bool bf16_in = !is_f32(x, "x");
+    TORCH_CHECK(x.dim() == 4, "x must be 4-D (",
+                to_nhwc ? "NCHW" : "NHWC", "), got ", x.dim(), "-D");
+    TORCH_CHECK(x.is_contiguous(), "x must be contiguous");
+    TORCH_CHECK(x.numel() < (1LL << 31), "x has 2^31 or more elements");
+    int64_t N = x.size(0), C, H, W;
+    if (to_nhwc) { C = x.size(1); H = x.size(2); W = x.size(3); }
+    else { H = x.size(1); W = x.size(2); C = x.size(3); }
+    std::vector<int64_t> shape =
+        to_nhwc ? std::vector<int64_t>{N, H, W, C}
+                : std::vector<int64_t>{N, C, H, W};
+    auto dt = bf16_out ? at::kBFloat16 : at::kFloat;
+    Tensor y;
+    if (out) {
+        TORCH_CHECK(out->is_cuda() && out->is_contiguous() &&
+                    out->scalar_type() == dt && out->sizes().vec() == shape,
+                    "out must be a contiguous GPU tensor of the converted "
+                    "shape and dtype");
+        y = *out;
+    } else {
+        y = at::empty(shape, x.options().dtype(dt));
+    }
+    defer_hip::launch_layout(bptr(x), bptr_mut(y), N, (int)C, H * W, to_nhwc,
+                             bf16_in, bf16_out, cur_stream());
+    return y;
+}
+
 std::tuple<int64_t, int64_t, int64_t> field_shape(const Tensor& t) {
     auto sz = t.sizes();
     int nd = sz.size();
@@ -1244,6 +1279,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("avgpool2d", &avgpool2d);
     m.def("concat_lastdim", &concat_lastdim);
     m.def("global_avg_pool", &global_avg_pool);
+    m.def("layout_convert", &layout_convert, py::arg("x"),
+          py::arg("to_nhwc"), py::arg("bf16_out"),
+          py::arg("out") = py::none());
     m.def("zfp_encode", &zfp_encode, py::arg("x"), py::arg("rate"),
           py::arg("out") = py::none(), py::arg("phases") = 3);
     m.def("zfp_decode", &zfp_decode);

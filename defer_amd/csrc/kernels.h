@@ -161,6 +161,13 @@ void launch_avgpool_f32(const float* x, float* y, int NB, int H, int W,
 void launch_gap_f32(const float* x, float* y, int NB, int HW, int C,
                     hipStream_t s);
 
+// NCHW <-> NHWC conversion with an optional fp32 <-> bf16 conversion in the
+// same pass (layout.hip). x is [N, C, HW] when to_nhwc, [N, HW, C]
+// otherwise, and y the other one; both contiguous. fp32 -> bf16 rounds to
+// nearest even. Offsets are 64-bit; N*C*HW < 2^31 is the bindings' rule.
+void launch_layout(const void* x, void* y, long N, int C, long HW,
+                   bool to_nhwc, bool bf16_in, bool bf16_out, hipStream_t s);
+
 // fixed-rate ZFP-style codec (see csrc/codec.hip / ops/zfp_ref.py)
 // phases: 3 = full encode; 1/2 run only the transform / serialize phase
 // (perf-bisection harness for tools/codecbench.py --phases)

@@ -162,13 +162,9 @@ class GraphModel(nn.Module):
                 for i, g in enumerate(self.graph.split(cut_points))]
 
 
-def from_torch(model: nn.Module) -> LayerGraph:
-    """FX-trace an arbitrary single-input nn.Module into a LayerGraph.
-
-    Capability parity with partitioning a user-provided Keras model
-    (dispatcher.py:107). Leaf modules become graph layers; call_function
-    nodes (e.g. `x + y`, torch.relu) become function layers.
-    """
+def fx_trace(model: nn.Module):
+    """FX-trace `model` with defer_amd layers (and every torch leaf module)
+    opaque. Returns (fx graph, {qualified name: module})."""
     import torch.fx as fx
 
     class LeafTracer(fx.Tracer):
@@ -178,70 +174,102 @@ def from_torch(model: nn.Module) -> LayerGraph:
                 return True
             return super().is_leaf_module(m, qualname)
 
-    tracer = LeafTracer()
-    g = tracer.trace(model)
-    modules = dict(model.named_modules())
+    return LeafTracer().trace(model), dict(model.named_modules())
+
+
+def fx_node_names(g) -> Dict[str, str]:
+    """LayerGraph name of every FX node of `g`. A leaf module called once
+    is named after its qualified name; one called more than once (a shared
+    `self.relu`) would repeat that name, so each of its calls takes the FX
+    node's own unique name (relu, relu_1, ...), as function and method
+    calls do."""
+    calls: Dict[str, int] = {}
+    for node in g.nodes:
+        if node.op == "call_module":
+            calls[node.target] = calls.get(node.target, 0) + 1
+    names = {}
+    for node in g.nodes:
+        if node.op == "placeholder":
+            names[node.name] = LayerGraph.INPUT
+        elif node.op == "call_module" and calls[node.target] == 1:
+            names[node.name] = node.target.replace(".", "_")
+        else:
+            names[node.name] = node.name
+    return names
+
+
+def fx_call_layer(node, modules):
+    """The layer that runs one FX call node as a LayerGraph node, and the
+    FX names of its tensor inputs in call order."""
+    import torch.fx as fx
+
+    if node.op == "call_module":
+        return modules[node.target], [a.name for a in node.args]
+    fn = node.target
+    if node.op == "call_method":
+        meth = node.target
+
+        def fn(x, *a, _m=meth, **k):
+            return getattr(x, _m)(*a, **k)
+
+    # Tensor inputs can appear anywhere in the argument tree
+    # (e.g. torch.cat([a, b], dim=-1)): replace every fx.Node
+    # with a positional placeholder and rebuild at call time.
+    class _Ref:
+        __slots__ = ("i",)
+
+        def __init__(self, i):
+            self.i = i
+
+    refs: List[str] = []
+
+    def scan(a):
+        if isinstance(a, fx.Node):
+            refs.append(a.name)
+            return _Ref(len(refs) - 1)
+        if isinstance(a, (list, tuple)):
+            return type(a)(scan(x) for x in a)
+        return a
+
+    sargs = tuple(scan(a) for a in node.args)
+    skwargs = {k: scan(v) for k, v in node.kwargs.items()}
+
+    def wrapped(*tensors, _fn=fn, _sa=sargs, _sk=skwargs, _Ref=_Ref):
+        def subst(a):
+            if isinstance(a, _Ref):
+                return tensors[a.i]
+            if isinstance(a, (list, tuple)):
+                return type(a)(subst(x) for x in a)
+            return a
+
+        return _fn(*(subst(a) for a in _sa),
+                   **{k: subst(v) for k, v in _sk.items()})
+
+    return wrapped, refs
+
+
+def from_torch(model: nn.Module) -> LayerGraph:
+    """FX-trace an arbitrary single-input nn.Module into a LayerGraph.
+
+    Capability parity with partitioning a user-provided Keras model
+    (dispatcher.py:107). Leaf modules become graph layers; call_function
+    nodes (e.g. `x + y`, torch.relu) become function layers. The layers
+    are torch's own and run in the model's NCHW layout; `defer_amd.lower`
+    rewrites them onto the project's NHWC HIP layers.
+    """
+    g, modules = fx_trace(model)
+    name_map = fx_node_names(g)
     nodes: List[GraphNode] = []
-    name_map: Dict[str, str] = {}
     placeholder = None
     for node in g.nodes:
         if node.op == "placeholder":
             if placeholder is not None:
                 raise ValueError("only single-input models are supported")
             placeholder = node.name
-            name_map[node.name] = LayerGraph.INPUT
-        elif node.op == "call_module":
-            mod = modules[node.target]
-            ins = [name_map[a.name] for a in node.args]
-            nm = node.target.replace(".", "_")
-            nodes.append(GraphNode(nm, mod, ins))
-            name_map[node.name] = nm
-        elif node.op == "call_function" or node.op == "call_method":
-            fn = node.target
-            if node.op == "call_method":
-                meth = node.target
-
-                def fn(x, *a, _m=meth, **k):
-                    return getattr(x, _m)(*a, **k)
-
-            # Tensor inputs can appear anywhere in the argument tree
-            # (e.g. torch.cat([a, b], dim=-1)): replace every fx.Node
-            # with a positional placeholder and rebuild at call time.
-            class _Ref:
-                __slots__ = ("i",)
-
-                def __init__(self, i):
-                    self.i = i
-
-            refs: List[str] = []
-
-            def scan(a):
-                if isinstance(a, fx.Node):
-                    refs.append(a.name)
-                    return _Ref(len(refs) - 1)
-                if isinstance(a, (list, tuple)):
-                    return type(a)(scan(x) for x in a)
-                return a
-
-            sargs = tuple(scan(a) for a in node.args)
-            skwargs = {k: scan(v) for k, v in node.kwargs.items()}
-            ins = [name_map[r] for r in refs]
-            nm = node.name
-
-            def wrapped(*tensors, _fn=fn, _sa=sargs, _sk=skwargs,
-                        _Ref=_Ref):
-                def subst(a):
-                    if isinstance(a, _Ref):
-                        return tensors[a.i]
-                    if isinstance(a, (list, tuple)):
-                        return type(a)(subst(x) for x in a)
-                    return a
-
-                return _fn(*(subst(a) for a in _sa),
-                           **{k: subst(v) for k, v in _sk.items()})
-
-            nodes.append(GraphNode(nm, wrapped, ins))
-            name_map[node.name] = nm
+        elif node.op in ("call_module", "call_function", "call_method"):
+            layer, refs = fx_call_layer(node, modules)
+            nodes.append(GraphNode(name_map[node.name], layer,
+                                   [name_map[r] for r in refs]))
         elif node.op == "output":
             out_arg = node.args[0]
             return LayerGraph(nodes, output=name_map[out_arg.name])

@@ -194,3 +194,59 @@ class Dense(nn.Module):
 class Softmax(nn.Module):
     def forward(self, x):
         return ops.softmax(x)
+
+
+class Relu(nn.Module):
+    """A ReLU that no conv, BN, add or dense layer could take in."""
+
+    def forward(self, x):
+        return ops.relu(x)
+
+
+class ToNHWC(nn.Module):
+    """NCHW -> NHWC at the border of a lowered torch model: its input, and
+    the output of a layer that stayed torch code (defer_amd.lower)."""
+
+    def forward(self, x):
+        return ops.to_nhwc(x.contiguous())
+
+
+class ToNCHW(nn.Module):
+    """NHWC -> NCHW: the inverse border, into torch code or out of the
+    model, so the user gets the tensor their model would have given."""
+
+    def forward(self, x):
+        return ops.to_nchw(x.contiguous())
+
+
+class TorchIsland(nn.Module):
+    """A piece of a torch model that was not lowered and runs as torch
+    code, in NCHW, among defer_amd layers. `inner` is the leaf module or
+    the function layer `from_torch` would have built; `reason` says why it
+    stayed. StageExecutor casts matrices to the compute dtype and vectors
+    to fp32, which a plain torch module (bf16 weight, fp32 bias) rejects:
+    a module island therefore follows its input, casting its own floating
+    parameters and buffers to the incoming dtype when that changes."""
+
+    def __init__(self, inner, reason=""):
+        super().__init__()
+        if isinstance(inner, nn.Module):
+            self.inner = inner
+        else:
+            self.inner = None
+            self._fn = inner
+        self.reason = reason
+        self._dtype = None
+
+    def forward(self, *args):
+        if self.inner is None:
+            return self._fn(*args)
+        dt = next((a.dtype for a in args if torch.is_tensor(a)
+                   and a.is_floating_point()), None)
+        if dt is not None and dt != self._dtype:
+            self.inner.to(dt)
+            self._dtype = dt
+        return self.inner(*args)
+
+    def extra_repr(self):
+        return f"kept: {self.reason}"

@@ -321,6 +321,46 @@ def global_avg_pool(x):
     return m.global_avg_pool(x)
 
 
+_LAYOUT_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def _layout_convert(x, dtype, out, to_nhwc):
+    name = "to_nhwc" if to_nhwc else "to_nchw"
+    dtype = x.dtype if dtype is None else dtype
+    # the same rejections on every device, so a model that lowers on the
+    # CPU cannot fail on these later on the GPU
+    if x.dtype not in _LAYOUT_DTYPES or dtype not in _LAYOUT_DTYPES:
+        raise RuntimeError(
+            f"{name}: x and dtype must be bf16 or fp32, got {x.dtype} -> "
+            f"{dtype}")
+    if x.dim() != 4:
+        raise RuntimeError(f"{name}: x must be 4-D, got {x.dim()}-D")
+    if not x.is_contiguous():
+        raise RuntimeError(f"{name}: x must be contiguous")
+    if x.numel() >= 2 ** 31:
+        raise RuntimeError(f"{name}: x has 2^31 or more elements")
+    m = _backend(x)
+    if m is None:
+        ref = _ref.to_nhwc if to_nhwc else _ref.to_nchw
+        y = ref(x, dtype)
+        return y if out is None else out.copy_(y)
+    return m.layout_convert(x, to_nhwc, dtype == torch.bfloat16, out)
+
+
+def to_nhwc(x, dtype=None, out=None):
+    """[N, C, H, W] -> a fresh contiguous [N, H, W, C] tensor of `dtype`
+    (None = x's). x is contiguous fp32 or bf16; fp32 -> bf16 rounds to
+    nearest even like x.to(torch.bfloat16), bf16 -> fp32 is exact. One HIP
+    launch on the GPU (csrc/layout.hip). out: a contiguous tensor of the
+    result's shape and dtype to write into instead of allocating."""
+    return _layout_convert(x, dtype, out, True)
+
+
+def to_nchw(x, dtype=None, out=None):
+    """[N, H, W, C] -> [N, C, H, W]; the inverse of to_nhwc, same rules."""
+    return _layout_convert(x, dtype, out, False)
+
+
 def linear(x, w, bias=None):
     m = _backend(x)
     if m is None:

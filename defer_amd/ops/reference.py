@@ -103,6 +103,17 @@ def linear(x, w, bias=None):
     return y.to(x.dtype)
 
 
+def to_nhwc(x, dtype):
+    """[N, C, H, W] -> [N, H, W, C] in `dtype` (fp32 -> bf16 rounds to
+    nearest even, bf16 -> fp32 is exact)."""
+    return x.permute(0, 2, 3, 1).contiguous().to(dtype)
+
+
+def to_nchw(x, dtype):
+    """[N, H, W, C] -> [N, C, H, W] in `dtype`; the inverse of to_nhwc."""
+    return x.permute(0, 3, 1, 2).contiguous().to(dtype)
+
+
 def softmax(x):
     """Row softmax over the last dim (classifier head)."""
     return F.softmax(x.float(), dim=-1).to(x.dtype)

@@ -31,20 +31,29 @@ XGMI_LINK_GBPS = 153.0
 EFF_TFLOPS = 287.0
 
 
-def as_graph_model(model) -> GraphModel:
+def as_graph_model(model, cfg=None) -> GraphModel:
+    """`cfg`: a PipelineConfig; with cfg.lower a plain nn.Module is lowered
+    onto the NHWC HIP layers (defer_amd.lower) instead of keeping torch's
+    own layers as leaves."""
     if isinstance(model, GraphModel):
         return model
     if isinstance(model, LayerGraph):
         return GraphModel(model)
     if isinstance(model, nn.Module):
+        if cfg is not None and cfg.lower:
+            from defer_amd.lower import lower_torch
+
+            return GraphModel(lower_torch(model, cfg.input_shape),
+                              name=type(model).__name__)
         return GraphModel(from_torch(model), name=type(model).__name__)
     raise TypeError(f"cannot partition {type(model)!r}")
 
 
-def partition_model(model, cut_points: List[str]) -> List[GraphModel]:
+def partition_model(model, cut_points: List[str],
+                    cfg=None) -> List[GraphModel]:
     """Split at named layers into len(cut_points)+1 stage models
     (part1..partN, dispatcher.py:27-42)."""
-    gm = as_graph_model(model)
+    gm = as_graph_model(model, cfg)
     return gm.stage_models(list(cut_points))
 
 

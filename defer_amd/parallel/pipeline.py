@@ -174,7 +174,7 @@ class DEFER:
         if partition_layers is None:
             from defer_amd.parallel.calibrate import find_calibration
 
-            gm0 = as_graph_model(model)
+            gm0 = as_graph_model(model, cfg)
             partition_layers, stages = auto_partition(
                 gm0, n,
                 input_shape=tuple(cfg.input_shape)
@@ -182,7 +182,7 @@ class DEFER:
                 measured_us=find_calibration(gm0.model_name,
                                              cfg.calibration_file))
         else:
-            stages = partition_model(model, partition_layers)
+            stages = partition_model(model, partition_layers, cfg)
         if len(stages) != n:
             raise ValueError(
                 f"{len(stages)} stages for {n} compute nodes")
@@ -288,7 +288,7 @@ class DistPipeline:
                       else torch.float32)
         self.batch_shape = tuple(batch_shape)
 
-        gm = as_graph_model(model)
+        gm = as_graph_model(model, cfg)
         if cfg.weights_dir and cfg.partition_layers is None:
             # partition exactly as the checkpoint was partitioned
             from defer_amd import checkpoint

@@ -20,7 +20,7 @@ CSRC = ROOT / "defer_amd" / "csrc"
 
 sources = [str(CSRC / f) for f in
            ["bindings.cpp", "conv.hip", "conv_ws.hip", "prebn.hip", "chain.hip", "stem_pool.hip", "elementwise.hip", "pool.hip",
-            "codec.hip", "lz4.hip", "pack.hip", "conv_f32.hip", "ops_f32.hip"]
+            "layout.hip", "codec.hip", "lz4.hip", "pack.hip", "conv_f32.hip", "ops_f32.hip"]
            if (CSRC / f).exists()]
 
 setup(
