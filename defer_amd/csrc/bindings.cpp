@@ -6,6 +6,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include <cmath>
 #include <cstdlib>
 #include <functional>
 #include <mutex>
@@ -52,6 +53,15 @@ void check_f32(const Tensor& t, const char* name) {
 }
 
 const float* f32ptr(const Tensor& t) { return t.data_ptr<float>(); }
+
+// activation codes of the ops that know ReLU6 (ACT_* of csrc/common.h);
+// C++ callers that pass a bool get none / relu
+enum { kActNone = 0, kActRelu = 1, kActRelu6 = 2 };
+
+void check_act(int64_t act) {
+    TORCH_CHECK(act >= kActNone && act <= kActRelu6,
+                "act must be 0 (none), 1 (relu) or 2 (relu6), got ", act);
+}
 
 // 16B zero source for OOB global_load_lds lanes, one per process
 const void* zero_buf() {
@@ -155,7 +165,7 @@ const float* f32_vec_opt(const c10::optional<Tensor>& t, const char* name,
 void run_conv_f32(const Tensor& x, const Tensor& w, const float* scale,
                   const float* bias, const c10::optional<Tensor>& res,
                   Tensor& out, long M, int H, int W, int Cin, int OH, int OW,
-                  int R, int S, int stride, int pad, bool relu) {
+                  int R, int S, int stride, int pad, int act) {
     int Cout = (int)out.size(-1);
     TORCH_CHECK(M < (1LL << 31), "M too large");
     TORCH_CHECK(x.numel() < (1LL << 31), "x has 2^31 or more elements");
@@ -175,7 +185,7 @@ void run_conv_f32(const Tensor& x, const Tensor& w, const float* scale,
     p.M = (int)M; p.K = R * S * Cin; p.Cout = Cout;
     p.H = H; p.W = W; p.Cin = Cin;
     p.OH = OH; p.OW = OW; p.S = S; p.stride = stride; p.pad = pad;
-    p.relu = relu;
+    p.relu = act;
     bool gemm_mode = (R == 1 && S == 1 && stride == 1 && pad == 0);
     if (M > 0)
         defer_hip::launch_conv_f32(p, gemm_mode, conv_f32_tile(),
@@ -186,7 +196,7 @@ Tensor conv2d_bn_act_f32(const Tensor& x, const Tensor& w,
                          const c10::optional<Tensor>& scale,
                          const c10::optional<Tensor>& bias,
                          const c10::optional<Tensor>& res, int64_t stride,
-                         int64_t pad, bool relu) {
+                         int64_t pad, int act) {
     check_f32(x, "x");
     check_f32(w, "w");
     TORCH_CHECK(x.dim() == 4, "x must be NHWC");
@@ -222,11 +232,11 @@ Tensor conv2d_bn_act_f32(const Tensor& x, const Tensor& w,
             return t;
         });
         run_conv_f32(xp, wp, sc, bi, res, out, M, H, W, C4, OH, OW, R, S,
-                     (int)stride, (int)pad, relu);
+                     (int)stride, (int)pad, act);
         return out;
     }
     run_conv_f32(x, w, sc, bi, res, out, M, H, W, Cin, OH, OW, R, S,
-                 (int)stride, (int)pad, relu);
+                 (int)stride, (int)pad, act);
     return out;
 }
 
@@ -241,7 +251,7 @@ Tensor linear_f32(const Tensor& x, const Tensor& w,
     TORCH_CHECK(N % 4 == 0, "fp32 linear needs N % 4 == 0, got ", N);
     auto out = at::empty({M, N}, x.options());
     run_conv_f32(x, w, nullptr, f32_vec_opt(bias, "bias", N), c10::nullopt,
-                 out, M, 1, 1, K, 1, 1, 1, 1, 1, 0, false);
+                 out, M, 1, 1, K, 1, 1, 1, 1, 1, 0, kActNone);
     return out;
 }
 
@@ -278,6 +288,7 @@ ConvParams conv_geom(long M, int K, int Cout, int NB, int H, int W, int Cin,
     p.NB = NB; p.H = H; p.W = W; p.Cin = Cin;
     p.OH = OH; p.OW = OW; p.R = R; p.S = S;
     p.stride = stride; p.pad = pad;
+    p.act_hi = INFINITY;            // plain ReLU; conv2d_bn_act sets ReLU6's
     if (gemm_mode) {
         p.NB = (int)M; p.H = 1; p.W = 1; p.Cin = K;
         p.OH = 1; p.OW = 1;
@@ -421,15 +432,20 @@ py::dict conv_plan(std::vector<int64_t> xs, std::vector<int64_t> ws,
 // launch_conv_igemm paths for the 3x3/s1/p1 64->64 bf16 class: 0 = the
 // measured policy, 1 = the new kernel wherever it covers the shape, 2 =
 // never. Shapes it does not cover run launch_conv_igemm under every mode.
-// max_blocks caps that kernel's grid (0 = policy).
+// max_blocks caps that kernel's grid (0 = policy). act: kActNone, kActRelu
+// or kActRelu6; ReLU6 runs the ReLU instantiation of whichever kernel the
+// plan names, with the upper bound 6 in ConvParams::act_hi.
 Tensor conv2d_bn_act(Tensor x, Tensor w, c10::optional<Tensor> scale,
                      c10::optional<Tensor> bias, c10::optional<Tensor> res,
-                     int64_t stride, int64_t pad, bool relu,
+                     int64_t stride, int64_t pad, int64_t act,
                      int64_t mode = 0, int64_t max_blocks = 0) {
     TORCH_CHECK(mode >= 0 && mode <= 2, "mode must be 0, 1 or 2");
     TORCH_CHECK(max_blocks >= 0, "max_blocks must be >= 0");
+    check_act(act);
     if (is_f32(x, "x"))
-        return conv2d_bn_act_f32(x, w, scale, bias, res, stride, pad, relu);
+        return conv2d_bn_act_f32(x, w, scale, bias, res, stride, pad,
+                                 (int)act);
+    const bool relu = act != kActNone;
     check_bf16(x, "x");
     check_bf16(w, "w");
     TORCH_CHECK(x.dim() == 4, "x must be NHWC");
@@ -450,6 +466,7 @@ Tensor conv2d_bn_act(Tensor x, Tensor w, c10::optional<Tensor> scale,
     p.res = res ? bptr(*res) : nullptr;
     p.out = bptr_mut(out);
     p.zbuf = zero_buf();
+    if (act == kActRelu6) p.act_hi = 6.0f;
 
     Tensor xp = x, wp = w;
     if (g.path == ConvPrep::SWIN) {
@@ -754,6 +771,95 @@ Tensor relu(Tensor x) {
     auto out = at::empty_like(x);
     defer_hip::launch_relu(bptr(x), bptr_mut(out), x.numel() / 8,
                            cur_stream());
+    return out;
+}
+
+Tensor relu6(Tensor x) {
+    if (is_f32(x, "x")) {
+        check_f32(x, "x");
+        TORCH_CHECK(x.numel() % 4 == 0, "fp32 relu6 needs numel % 4 == 0");
+        auto out = at::empty_like(x);
+        defer_hip::launch_relu6_f32(f32ptr(x), out.data_ptr<float>(),
+                                    x.numel() / 4, cur_stream());
+        return out;
+    }
+    check_bf16(x, "x");
+    TORCH_CHECK(x.numel() % 8 == 0, "numel must be a multiple of 8");
+    auto out = at::empty_like(x);
+    defer_hip::launch_relu6(bptr(x), bptr_mut(out), x.numel() / 8,
+                            cur_stream());
+    return out;
+}
+
+// fp32[C] scale / bias of the depthwise conv; absent = the cached ones /
+// zeros, which bound C
+const float* dw_vec_opt(const c10::optional<Tensor>& t, const char* name,
+                        const float* fallback, int64_t C) {
+    if (!t) {
+        TORCH_CHECK(C <= 8192, "dwconv2d_bn_act without ", name,
+                    " takes at most C = 8192, got ", C);
+        return fallback;
+    }
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat &&
+                t->is_contiguous() && t->numel() == C,
+                name, " must be a contiguous GPU fp32[C]");
+    return t->data_ptr<float>();
+}
+
+// Depthwise conv + folded BN + activation (csrc/dwconv.hip): x NHWC, w
+// [R, S, C], both bf16 or both fp32. Everything the kernels do not serve
+// is refused here; there is no other path.
+Tensor dwconv2d_bn_act(Tensor x, Tensor w, c10::optional<Tensor> scale,
+                       c10::optional<Tensor> bias, int64_t stride,
+                       int64_t pad, int64_t act) {
+    check_act(act);
+    const bool f32 = is_f32(x, "x");
+    if (f32) {
+        check_f32(x, "x");
+        check_f32(w, "w");
+    } else {
+        check_bf16(x, "x");
+        check_bf16(w, "w");
+        TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 &&
+                    (uintptr_t)w.data_ptr() % 16 == 0,
+                    "x and w must be 16-byte aligned");
+    }
+    TORCH_CHECK(x.dim() == 4, "x must be NHWC");
+    TORCH_CHECK(w.dim() == 3, "w must be [R, S, C]");
+    int64_t NB = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+    int64_t R = w.size(0), S = w.size(1);
+    TORCH_CHECK(w.size(2) == C, "w has ", w.size(2), " channels, x has ", C);
+    TORCH_CHECK(R == S && (R == 3 || R == 5),
+                "depthwise conv needs a 3x3 or 5x5 kernel, got ", R, "x", S);
+    TORCH_CHECK(stride == 1 || stride == 2,
+                "depthwise conv needs stride 1 or 2, got ", stride);
+    TORCH_CHECK(pad >= 0 && pad <= R / 2,
+                "depthwise conv needs 0 <= padding <= R / 2, got ", pad);
+    const int vec = f32 ? 4 : 8;
+    TORCH_CHECK(C > 0 && C % vec == 0, f32 ? "fp32" : "bf16",
+                " depthwise conv needs C % ", vec, " == 0, got ", C);
+    TORCH_CHECK(H + 2 * pad >= R && W + 2 * pad >= S,
+                "kernel larger than the padded input");
+    TORCH_CHECK(x.numel() < (1LL << 31), "x has 2^31 or more elements");
+    int64_t OH = (H + 2 * pad - R) / stride + 1;
+    int64_t OW = (W + 2 * pad - S) / stride + 1;
+    TORCH_CHECK(NB * OH * OW * C < (1LL << 31),
+                "out has 2^31 or more elements");
+    const float* sc = dw_vec_opt(scale, "scale", ones_buf(), C);
+    const float* bi = dw_vec_opt(bias, "bias", zeros_buf(), C);
+    auto out = at::empty({NB, OH, OW, C}, x.options());
+    if (out.numel() == 0) return out;
+    if (f32)
+        defer_hip::launch_dwconv_f32(f32ptr(x), f32ptr(w), sc, bi,
+                                     out.data_ptr<float>(), (int)NB, (int)H,
+                                     (int)W, (int)C, (int)OH, (int)OW,
+                                     (int)R, (int)stride, (int)pad,
+                                     (int)act, cur_stream());
+    else
+        defer_hip::launch_dwconv(bptr(x), bptr(w), sc, bi, bptr_mut(out),
+                                 (int)NB, (int)H, (int)W, (int)C, (int)OH,
+                                 (int)OW, (int)R, (int)stride, (int)pad,
+                                 (int)act, cur_stream());
     return out;
 }
 
@@ -1241,8 +1347,11 @@ Tensor pack_decode(Tensor wire, std::vector<int64_t> shape, bool bf16_out) {
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("conv2d_bn_act", &conv2d_bn_act, py::arg("x"), py::arg("w"),
           py::arg("scale"), py::arg("bias"), py::arg("res"),
-          py::arg("stride"), py::arg("pad"), py::arg("relu"),
+          py::arg("stride"), py::arg("pad"), py::arg("act"),
           py::arg("mode") = 0, py::arg("max_blocks") = 0);
+    m.def("dwconv2d_bn_act", &dwconv2d_bn_act, py::arg("x"), py::arg("w"),
+          py::arg("scale"), py::arg("bias"), py::arg("stride"),
+          py::arg("pad"), py::arg("act"));
     m.def("conv_ws_stats", &conv_ws_stats);
     m.def("conv_plan", &conv_plan, py::arg("x_shape"), py::arg("w_shape"),
           py::arg("stride"), py::arg("pad"), py::arg("has_res"),
@@ -1274,6 +1383,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("stem_pool_stats", &stem_pool_stats);
     m.def("add_act", &add_act);
     m.def("relu", &relu);
+    m.def("relu6", &relu6);
     m.def("softmax", &softmax);
     m.def("maxpool2d", &maxpool2d);
     m.def("avgpool2d", &avgpool2d);

@@ -38,8 +38,17 @@ __device__ __forceinline__ int cdiv(int a, int b) { return (a + b - 1) / b; }
     __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 
 // activation codes
-enum { ACT_NONE = 0, ACT_RELU = 1 };
+// (ACT_RELU6 is a runtime value of the depthwise and fp32 conv kernels and
+// of the bindings; the bf16 conv templates take ACT_RELU with a bound)
+enum { ACT_NONE = 0, ACT_RELU = 1, ACT_RELU6 = 2 };
 
 __device__ __forceinline__ float apply_act(float v, int act) {
     return act == ACT_RELU ? fmaxf(v, 0.0f) : v;
+}
+
+// The bf16 conv epilogues: ACT_RELU clamps to [0, hi]. hi = +inf is the
+// plain ReLU (min(v, +inf) == v, so the bits are those of apply_act) and
+// hi = 6 is ReLU6, without a third template value per kernel.
+__device__ __forceinline__ float apply_act_hi(float v, int act, float hi) {
+    return act == ACT_RELU ? fminf(fmaxf(v, 0.0f), hi) : v;
 }

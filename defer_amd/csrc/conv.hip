@@ -398,7 +398,7 @@ __global__ __launch_bounds__(TPB, WPS) void conv_igemm_kernel(
                     for (int j = 0; j < 8; ++j) {
                         float v = v4[i][j / 4][j % 4];
                         if (HAS_RES) v += bf2f(rv[i][j]);
-                        o[j] = f2bf(apply_act(v, ACT));
+                        o[j] = f2bf(apply_act_hi(v, ACT, p.act_hi));
                     }
                     *reinterpret_cast<bf16x8*>(OUT + off[i]) = o;
                 }
@@ -420,7 +420,7 @@ __global__ __launch_bounds__(TPB, WPS) void conv_igemm_kernel(
                         if (n + j >= p.Cout) continue;
                         float v = v4[j];
                         if (HAS_RES) v += bf2f(RES[off + j]);
-                        OUT[off + j] = f2bf(apply_act(v, ACT));
+                        OUT[off + j] = f2bf(apply_act_hi(v, ACT, p.act_hi));
                     }
                 }
             }
@@ -765,7 +765,7 @@ __global__ __launch_bounds__(TPB, WPS) void conv_win_kernel(
                     for (int j = 0; j < 8; ++j) {
                         float v = v4[i][j / 4][j % 4];
                         if (HAS_RES) v += bf2f(rv[i][j]);
-                        o[j] = f2bf(apply_act(v, ACT));
+                        o[j] = f2bf(apply_act_hi(v, ACT, p.act_hi));
                     }
                     *reinterpret_cast<bf16x8*>(OUT + off[i]) = o;
                 }
@@ -791,7 +791,7 @@ __global__ __launch_bounds__(TPB, WPS) void conv_win_kernel(
                         if (n + j >= p.Cout) continue;
                         float v = v4[j];
                         if (HAS_RES) v += bf2f(RES[off + j]);
-                        OUT[off + j] = f2bf(apply_act(v, ACT));
+                        OUT[off + j] = f2bf(apply_act_hi(v, ACT, p.act_hi));
                     }
                 }
             }
@@ -1139,7 +1139,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_swin_kernel(
                     bf16x8 o;
 #pragma unroll
                     for (int j = 0; j < 8; ++j)
-                        o[j] = f2bf(apply_act(v4[i][j / 4][j % 4], ACT));
+                        o[j] = f2bf(apply_act_hi(v4[i][j / 4][j % 4], ACT,
+                                                 p.act_hi));
                     *reinterpret_cast<bf16x8*>(OUT + off[i]) = o;
                 }
             } else {
@@ -1162,7 +1163,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_swin_kernel(
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         if (n + j >= p.Cout) continue;
-                        OUT[off + j] = f2bf(apply_act(v4[j], ACT));
+                        OUT[off + j] =
+                            f2bf(apply_act_hi(v4[j], ACT, p.act_hi));
                     }
                 }
             }

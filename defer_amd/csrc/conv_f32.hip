@@ -230,6 +230,10 @@ __global__ __launch_bounds__(F32_TPB) void conv_f32_kernel(
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
         }
+        if (p.relu == ACT_RELU6) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = fminf(v[e], 6.f);
+        }
         *reinterpret_cast<f32x4*>(out + o) = v;
     }
 }

@@ -269,7 +269,7 @@ __global__ __launch_bounds__(WS_TPB, 2) void conv_ws_kernel(ConvParams p) {
                     for (int j = 0; j < 8; ++j) {
                         float v = v4[i][j / 4][j % 4];
                         if (HAS_RES) v += bf2f(rv[i][j]);
-                        o[j] = f2bf(apply_act(v, ACT));
+                        o[j] = f2bf(apply_act_hi(v, ACT, p.act_hi));
                     }
                     *reinterpret_cast<bf16x8*>(OUT + off[i]) = o;
                 }
@@ -292,7 +292,7 @@ __global__ __launch_bounds__(WS_TPB, 2) void conv_ws_kernel(ConvParams p) {
                     for (int j = 0; j < 4; ++j) {
                         float v = v4[j];
                         if (HAS_RES) v += bf2f(RES[off + j]);
-                        OUT[off + j] = f2bf(apply_act(v, ACT));
+                        OUT[off + j] = f2bf(apply_act_hi(v, ACT, p.act_hi));
                     }
                 }
             }

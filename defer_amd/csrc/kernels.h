@@ -25,6 +25,10 @@ struct ConvParams {
     // full-sync debug flag (ConvPlan::full_sync, DEFER_CONV_VARIANT=W,
     // forces vmcnt(0) drains every phase).
     unsigned int owmul, ohmul, cmul, smul;
+    // upper bound of the ReLU epilogues (the relu kernels clamp to
+    // [0, act_hi]): +inf for ReLU, which leaves every bit as it was, 6 for
+    // ReLU6. Unused when the kernel has no activation.
+    float act_hi;
 };
 
 void launch_pad_channels(const void* x, void* y, long rows, int C, int C8,
@@ -103,6 +107,7 @@ void launch_bn_act(const void* x, const float* scale, const float* bias,
 void launch_add_act(const void* a, const void* b, void* y, long total8,
                     bool relu, hipStream_t s);
 void launch_relu(const void* x, void* y, long total8, hipStream_t s);
+void launch_relu6(const void* x, void* y, long total8, hipStream_t s);
 // two-input NHWC channel concat (c1, c2 % 8 == 0)
 void launch_cat2(const void* a, const void* b, void* y, long rows,
                  int c1, int c2, hipStream_t s);
@@ -132,7 +137,7 @@ struct ConvF32Params {
     int M, K, Cout;
     int H, W, Cin;
     int OH, OW, S, stride, pad;
-    int relu;
+    int relu;           // ACT_NONE, ACT_RELU or ACT_RELU6 of common.h
 };
 // tile: 0 = heuristic, 1 = 128x128, 2 = 128x64 (A/B measurement switch)
 void launch_conv_f32(const ConvF32Params& p, bool gemm_mode, int tile,
@@ -148,6 +153,7 @@ void launch_bn_act_f32(const float* x, const float* scale, const float* bias,
 void launch_add_act_f32(const float* a, const float* b, float* y,
                         long total4, bool relu, hipStream_t s);
 void launch_relu_f32(const float* x, float* y, long total4, hipStream_t s);
+void launch_relu6_f32(const float* x, float* y, long total4, hipStream_t s);
 void launch_cat2_f32(const float* a, const float* b, float* y, long rows,
                      int c1, int c2, hipStream_t s);
 void launch_softmax_f32(const float* x, float* y, int rows, int cols,
@@ -160,6 +166,19 @@ void launch_avgpool_f32(const float* x, float* y, int NB, int H, int W,
                         hipStream_t s);
 void launch_gap_f32(const float* x, float* y, int NB, int HW, int C,
                     hipStream_t s);
+
+// depthwise conv + folded BN + activation (dwconv.hip), NHWC x and [R][S][C]
+// w with R == S in {3, 5}, stride in {1, 2}, 0 <= pad <= R / 2; C % 8 == 0
+// (bf16) or C % 4 == 0 (fp32); scale and bias non-null fp32[C]; act is
+// ACT_NONE, ACT_RELU or ACT_RELU6. Element offsets are 64-bit.
+void launch_dwconv(const void* x, const void* w, const float* scale,
+                   const float* bias, void* y, int NB, int H, int W, int C,
+                   int OH, int OW, int R, int stride, int pad, int act,
+                   hipStream_t s);
+void launch_dwconv_f32(const float* x, const float* w, const float* scale,
+                       const float* bias, float* y, int NB, int H, int W,
+                       int C, int OH, int OW, int R, int stride, int pad,
+                       int act, hipStream_t s);
 
 // NCHW <-> NHWC conversion with an optional fp32 <-> bf16 conversion in the
 // same pass (layout.hip). x is [N, C, HW] when to_nhwc, [N, HW, C]

@@ -60,6 +60,18 @@ __global__ void relu_f32_kernel(const float* __restrict__ x,
     }
 }
 
+__global__ void relu6_f32_kernel(const float* __restrict__ x,
+                                 float* __restrict__ y, long total4) {
+    long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    long stride = (long)gridDim.x * blockDim.x;
+    for (long i = i0; i < total4; i += stride) {
+        f32x4 v = ld4(x + i * 4), o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = fminf(fmaxf(v[j], 0.0f), 6.0f);
+        st4(y + i * 4, o);
+    }
+}
+
 // Row softmax: one wave per row, arbitrary ncols, accurate expf.
 __global__ void softmax_f32_kernel(const float* __restrict__ x,
                                    float* __restrict__ y, int rows,
@@ -190,6 +202,11 @@ void launch_add_act_f32(const float* a, const float* b, float* y,
 void launch_relu_f32(const float* x, float* y, long total4, hipStream_t s) {
     hipLaunchKernelGGL(relu_f32_kernel, dim3(grid1d(total4, 256)), dim3(256),
                        0, s, x, y, total4);
+}
+
+void launch_relu6_f32(const float* x, float* y, long total4, hipStream_t s) {
+    hipLaunchKernelGGL(relu6_f32_kernel, dim3(grid1d(total4, 256)),
+                       dim3(256), 0, s, x, y, total4);
 }
 
 void launch_cat2_f32(const float* a, const float* b, float* y, long rows,

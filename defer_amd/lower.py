@@ -15,6 +15,26 @@ NHWC; where a consumer needs the other layout one conversion node per
 (value, layout) is inserted, named `<producer>__nhwc` / `<producer>__nchw`,
 and shared between consumers.
 
+The patterns:
+
+    Conv2d [+ BatchNorm2d] [+ ReLU | ReLU6]        -> ConvBNAct
+    depthwise Conv2d [+ BatchNorm2d] [+ ReLU | ReLU6]
+        (groups == in == out channels, 3x3 or 5x5, stride 1 or 2,
+         padding <= k // 2, C % 8 == 0)            -> DepthwiseConvBNAct
+    BatchNorm2d [+ ReLU]                           -> BNAct
+    a + b [+ ReLU]                                 -> AddAct
+    Linear [+ ReLU]                                -> Dense
+    ReLU anywhere else                             -> Relu
+    ReLU6 anywhere else                            -> Relu6
+    MaxPool2d / AvgPool2d                          -> MaxPool / AvgPool
+    AdaptiveAvgPool2d(1) or F.adaptive_avg_pool2d(x, 1) + flatten,
+        mean over dims (2, 3)                      -> GlobalAvgPool
+    cat over dim 1, flatten into Linear, softmax   -> Concat, Flatten, Softmax
+
+ReLU6 is `nn.ReLU6`, `F.relu6`, `nn.Hardtanh(0., 6.)` or
+`F.hardtanh(x, 0., 6.)`. Every other grouped conv (groups between 1 and C,
+a channel multiplier) stays an island.
+
 A pattern (conv [+ BN] [+ ReLU], add [+ ReLU], linear [+ ReLU], ...) is
 fused only through intermediates with exactly one consumer, and the fused
 node takes the name of the pattern's last node, so a cut name that refers
@@ -23,7 +43,7 @@ HIP op accepts its shape in both compute dtypes (the `TORCH_CHECK`s of
 `csrc/bindings.cpp`); anything else stays an island, with the reason
 recorded in the `TorchIsland` that wraps it.
 
-In-place ops: torch writes an in-place ReLU or `a += b` into its input,
+In-place ops: torch writes an in-place ReLU, ReLU6 or `a += b` into its input,
 so a later reader of that tensor sees the result. The lowered ops are out
 of place; such a node, when its input has other readers, is emitted on
 its own and the input's name is rebound to its output for everything that
@@ -54,6 +74,8 @@ _VEC = 8            # bn_act / pools / global_avg_pool: C; add_act / relu:
 #                     numel; bf16 linear: K (fp32: K % 4)
 _COUT_VEC = 4       # fp32 conv: Cout % 4; fp32 linear: N % 4
 _MAX_NO_SCALE = 8192    # conv without a scale vector: cached ones[8192]
+_DW_KERNELS = (3, 5)    # depthwise conv (csrc/dwconv.hip): square kernels,
+_DW_STRIDES = (1, 2)    # strides, 0 <= padding <= k // 2, C % _VEC == 0
 
 
 def _pair(v):
@@ -151,18 +173,43 @@ class _Lowering:
             return n.target in (torch.relu, F.relu, torch.relu_, F.relu_)
         return n.op == "call_method" and n.target in ("relu", "relu_")
 
+    @staticmethod
+    def _arg(n, i, name, default):
+        return n.args[i] if len(n.args) > i else n.kwargs.get(name, default)
+
+    def is_relu6(self, n, of) -> bool:
+        """nn.ReLU6, F.relu6, nn.Hardtanh(0., 6.), F.hardtanh(x, 0., 6.)"""
+        if not n.args or n.args[0] is not of:
+            return False
+        if n.op == "call_module":
+            m = self.mod(n)
+            if type(m) is nn.ReLU6:
+                return True
+            return (type(m) is nn.Hardtanh and m.min_val == 0
+                    and m.max_val == 6)
+        if n.op != "call_function":
+            return False
+        if n.target is F.relu6:
+            return True
+        return (n.target in (F.hardtanh, F.hardtanh_)
+                and self._arg(n, 1, "min_val", -1.0) == 0
+                and self._arg(n, 2, "max_val", 1.0) == 6)
+
     def mutates_input(self, n) -> bool:
-        """An in-place ReLU or `a += b`: torch writes the result into
+        """An in-place ReLU, ReLU6 or `a += b`: torch writes the result into
         args[0], so every LATER reader of that tensor sees it."""
         if n.op == "call_module":
             m = self.mod(n)
-            return type(m) is nn.ReLU and m.inplace
+            return (type(m) in (nn.ReLU, nn.ReLU6, nn.Hardtanh)
+                    and m.inplace)
         if n.op == "call_function":
-            if n.target in (torch.relu_, F.relu_, operator.iadd):
+            if n.target in (torch.relu_, F.relu_, F.hardtanh_,
+                            operator.iadd):
                 return True
-            return n.target is F.relu and bool(
-                n.args[1] if len(n.args) > 1
-                else n.kwargs.get("inplace", False))
+            if n.target in (F.relu, F.relu6):
+                return bool(self._arg(n, 1, "inplace", False))
+            return n.target is F.hardtanh and bool(
+                self._arg(n, 3, "inplace", False))
         return n.op == "call_method" and n.target == "relu_"
 
     def rebind_mutated(self, n):
@@ -183,6 +230,17 @@ class _Lowering:
         then apply it), or None."""
         u = self.sole_user(n)
         return u if u is not None and self.is_relu(u, n) else None
+
+    def act_after(self, n):
+        """(node, "relu" | "relu6") for the activation that is `n`'s only
+        consumer, for the convs, whose kernels apply either; (None, "none")
+        otherwise."""
+        u = self.sole_user(n)
+        if u is not None and self.is_relu(u, n):
+            return u, "relu"
+        if u is not None and self.is_relu6(u, n):
+            return u, "relu6"
+        return None, "none"
 
     def is_flatten1(self, n, of) -> bool:
         """flatten(of, 1): nn.Flatten(), torch.flatten(x, 1), x.flatten(1)"""
@@ -221,8 +279,12 @@ class _Lowering:
         s = self.shape(n.args[0])
         if s is None or len(s) != 4:
             return "Conv2d on a value that is not 4-D"
-        if m.groups != 1:
-            return f"grouped conv (groups={m.groups})"
+        depthwise = (m.groups > 1 and m.groups == m.in_channels
+                     and m.groups == m.out_channels)
+        if m.groups != 1 and not depthwise:
+            return (f"grouped conv (groups={m.groups}, {m.in_channels} -> "
+                    f"{m.out_channels} channels): only depthwise convs "
+                    "(groups == in == out channels) are lowered")
         if _pair(m.dilation) != (1, 1):
             return f"dilated conv (dilation={tuple(m.dilation)})"
         if m.padding_mode != "zeros":
@@ -233,7 +295,17 @@ class _Lowering:
             return (f"conv geometry kernel={m.kernel_size} stride={m.stride} "
                     f"padding={m.padding}: needs a square kernel and equal "
                     "stride and padding in both dims")
-        if m.out_channels % _COUT_VEC:
+        if depthwise:
+            c = m.groups
+            if k not in _DW_KERNELS or st not in _DW_STRIDES or pad > k // 2:
+                return (f"depthwise conv (groups={c}) kernel={k} stride={st} "
+                        f"padding={pad}: the depthwise kernel takes "
+                        f"{_DW_KERNELS} kernels, strides {_DW_STRIDES} and "
+                        "padding <= kernel // 2")
+            if c % _VEC:
+                return (f"depthwise conv (groups={c}): the bf16 depthwise "
+                        f"kernel needs C % {_VEC} == 0")
+        elif m.out_channels % _COUT_VEC:
             return (f"Conv2d out_channels={m.out_channels}: the fp32 conv "
                     f"needs Cout % {_COUT_VEC} == 0")
         if s[2] + 2 * pad < k or s[3] + 2 * pad < k:
@@ -249,17 +321,23 @@ class _Lowering:
         if bn is None and m.out_channels > _MAX_NO_SCALE:
             return (f"Conv2d out_channels={m.out_channels} without a "
                     f"BatchNorm: more than {_MAX_NO_SCALE}")
-        r = self.relu_after(last)
+        r, act = self.act_after(last)
         if r is not None:
             chain.append(r)
             last = r
-        layer = L.ConvBNAct(m.in_channels, m.out_channels, kernel=k,
-                            stride=st, padding=pad,
-                            act="relu" if r is not None else "none",
-                            bn=bn is not None)
         w = m.weight.detach()
-        layer.weight = nn.Parameter(
-            w.permute(0, 2, 3, 1).contiguous().float())      # OIHW -> OHWI
+        if depthwise:
+            layer = L.DepthwiseConvBNAct(m.groups, kernel=k, stride=st,
+                                         padding=pad, act=act,
+                                         bn=bn is not None)
+            layer.weight = nn.Parameter(                # [C,1,R,S] -> RSC
+                w[:, 0].permute(1, 2, 0).contiguous().float())
+        else:
+            layer = L.ConvBNAct(m.in_channels, m.out_channels, kernel=k,
+                                stride=st, padding=pad, act=act,
+                                bn=bn is not None)
+            layer.weight = nn.Parameter(
+                w.permute(0, 2, 3, 1).contiguous().float())  # OIHW -> OHWI
         b = (m.bias.detach().double() if m.bias is not None
              else torch.zeros(m.out_channels, dtype=torch.float64))
         if bn is not None:
@@ -332,6 +410,21 @@ class _Lowering:
         self.rebind_mutated(n)
         return None
 
+    def lower_relu6(self, n) -> Optional[str]:
+        s = self.shape(n)
+        if s is None:
+            return "ReLU6 of a value of unknown shape"
+        numel = 1
+        for d in s:
+            numel *= d
+        if numel % _VEC:
+            return (f"ReLU6 of {numel} elements: relu6 needs "
+                    f"numel % {_VEC} == 0")
+        layout = NHWC if len(s) == 4 else None
+        self.emit(n, L.Relu6(), [self.use(n.args[0], layout)], layout, [n])
+        self.rebind_mutated(n)
+        return None
+
     def lower_pool(self, n) -> Optional[str]:
         m = self.mod(n)
         kind = type(m).__name__
@@ -372,9 +465,16 @@ class _Lowering:
         return None
 
     def lower_adaptive(self, n) -> Optional[str]:
+        """nn.AdaptiveAvgPool2d(1) or F.adaptive_avg_pool2d(x, 1)"""
+        import torch.fx as fx
+
         m = self.mod(n)
+        size = (m.output_size if m is not None
+                else self._arg(n, 1, "output_size", None))
+        if not n.args or not isinstance(n.args[0], fx.Node):
+            return "adaptive_avg_pool2d of something other than a tensor"
         s = self.shape(n.args[0])
-        if s is None or len(s) != 4 or _pair(m.output_size) != (1, 1):
+        if s is None or len(s) != 4 or _pair(size) != (1, 1):
             return "AdaptiveAvgPool2d other than a 4-D value to 1x1"
         u = self.sole_user(n)
         if u is None or not self.is_flatten1(u, n):
@@ -496,6 +596,8 @@ class _Lowering:
                 return self.lower_mean(n)
             if n.target in (F.softmax, torch.softmax):
                 return self.lower_softmax(n)
+            if n.target is F.adaptive_avg_pool2d:
+                return self.lower_adaptive(n)
         elif n.op == "call_method":
             if n.target == "mean":
                 return self.lower_mean(n)
@@ -503,6 +605,8 @@ class _Lowering:
                 return self.lower_softmax(n)
         if n.args and self.is_relu(n, n.args[0]):
             return self.lower_relu(n)
+        if n.args and self.is_relu6(n, n.args[0]):
+            return self.lower_relu6(n)
         if n.args and self.is_flatten1(n, n.args[0]):
             return self.lower_flatten(n)
         what = type(m).__name__ if m is not None else getattr(

@@ -3,7 +3,8 @@
 Each layer is a thin nn.Module over `defer_amd.ops` (HIP kernels on GPU,
 fp32 PyTorch reference on CPU). These are the in-repo replacements for the
 Keras layer zoo the reference executes via model.predict (node.py:106):
-Conv2D/BatchNorm/ReLU -> ConvBNAct (BN folded at init), Add(+ReLU) ->
+Conv2D/BatchNorm/ReLU -> ConvBNAct (BN folded at init), DepthwiseConv2D/
+BatchNorm/ReLU6 -> DepthwiseConvBNAct, Add(+ReLU) ->
 AddAct, MaxPooling2D -> MaxPool, GlobalAveragePooling2D -> GlobalAvgPool,
 Dense -> Dense, softmax -> Softmax.
 
@@ -22,7 +23,7 @@ from defer_amd import ops
 
 
 class ConvBNAct(nn.Module):
-    """Conv2d + folded inference BatchNorm + optional ReLU, fused.
+    """Conv2d + folded inference BatchNorm + optional ReLU or ReLU6, fused.
 
     BN folding: y = conv(x) * scale + bias with scale = gamma/sqrt(var+eps),
     bias = beta - mean*scale. Random init keeps BN-ish statistics so
@@ -55,6 +56,38 @@ class ConvBNAct(nn.Module):
 
     def flops_per_pixel(self):
         return 2 * self.kernel * self.kernel * self.cin * self.cout
+
+
+class DepthwiseConvBNAct(nn.Module):
+    """Depthwise Conv2d (one filter per channel) + folded inference
+    BatchNorm + optional ReLU / ReLU6, fused: the 3x3 layer between the
+    expand and project 1x1 convs of a MobileNetV2 block. The weight is
+    [R, S, C], channels last like the activation, and has 3 dims, so
+    StageExecutor casts it to the compute dtype with the conv weights."""
+
+    def __init__(self, c, kernel=3, stride=1, padding=None, act="relu6",
+                 bn=True):
+        super().__init__()
+        self.c = c
+        self.kernel, self.stride = kernel, stride
+        self.padding = (kernel // 2) if padding is None else padding
+        self.act = act
+        w = torch.randn(kernel, kernel, c) * math.sqrt(2.0 / (kernel * kernel))
+        self.weight = nn.Parameter(w)
+        self.scale = nn.Parameter(torch.ones(c)) if bn else None
+        self.bias = nn.Parameter(torch.zeros(c))
+
+    def forward(self, x):
+        return ops.dwconv2d_bn_act(
+            x, self.weight.to(x.dtype), self.scale, self.bias,
+            stride=self.stride, padding=self.padding, act=self.act)
+
+    def extra_repr(self):
+        return (f"depthwise {self.c} k{self.kernel} s{self.stride} "
+                f"p{self.padding} act={self.act}")
+
+    def flops_per_pixel(self):
+        return 2 * self.kernel * self.kernel * self.c
 
 
 class AddAct(nn.Module):
@@ -201,6 +234,13 @@ class Relu(nn.Module):
 
     def forward(self, x):
         return ops.relu(x)
+
+
+class Relu6(nn.Module):
+    """A ReLU6 that no conv or depthwise conv could take in."""
+
+    def forward(self, x):
+        return ops.relu6(x)
 
 
 class ToNHWC(nn.Module):

@@ -83,6 +83,20 @@ def _stats(name):
     return dict(getattr(_built(), name)())
 
 
+# activation names -> the codes of the bindings (ACT_* of csrc/common.h)
+_ACT_CODES = {"none": 0, "relu": 1, "relu6": 2}
+_RELU_OR_NONE = ("relu", "none")
+
+
+def _act_code(act, known=tuple(_ACT_CODES), what="act"):
+    """The binding's code of activation `act`. Every op checks its act
+    through this on every device, so a name the op does not implement
+    raises instead of silently meaning "none"."""
+    if act not in known:
+        raise ValueError(f"{what}={act!r}: expected one of {list(known)}")
+    return _ACT_CODES[act]
+
+
 # A/B switch for the weight-stationary 3x3 kernel (same convention as
 # DEFER_CONV_CHAIN): unset = the launcher's measured policy, "0" = always
 # the older conv paths, "force" = the new kernel wherever it covers the
@@ -99,15 +113,37 @@ def conv2d_bn_act(x, w, scale=None, bias=None, stride=1, padding=1,
     bit-identical to the general paths. mode: 0 = policy, 1 = that kernel
     wherever it covers the shape, 2 = never; None = DEFER_CONV_WS. Every
     other shape or dtype runs the general paths under every mode.
-    max_blocks caps that kernel's grid (0 = policy)."""
+    max_blocks caps that kernel's grid (0 = policy). act: "none", "relu" or
+    "relu6" (min(max(v, 0), 6)), applied after scale, bias and residual and
+    before the rounding to the output dtype."""
+    code = _act_code(act)
     m = _backend(x)
     if m is None:
         return _ref.conv2d_bn_act(x, w, scale, bias, stride, padding, act,
                                   residual)
     return m.conv2d_bn_act(x, w, scale, bias, residual, stride, padding,
-                           act == "relu",
+                           code,
                            _CONV_WS_MODE if mode is None else mode,
                            max_blocks)
+
+
+def dwconv2d_bn_act(x, w, scale=None, bias=None, stride=1, padding=1,
+                    act="none"):
+    """Depthwise conv + folded BN + activation, NHWC x and [R, S, C] w:
+
+        y[n, oh, ow, c] = act(scale[c] * sum_{r,s} x[n, oh*stride - pad + r,
+                              ow*stride - pad + s, c] * w[r, s, c] + bias[c])
+
+    scale and bias are fp32 [C] (None = 1 / 0); act as in conv2d_bn_act. On
+    the GPU one HIP kernel (csrc/dwconv.hip) for R == S in {3, 5}, stride
+    in {1, 2}, 0 <= padding <= R // 2 and C % 8 == 0 (bf16) or C % 4 == 0
+    (fp32); any other geometry raises. fp32 accumulation in the fixed tap
+    order (r, then s), one rounding at the end, run-to-run identical."""
+    code = _act_code(act)
+    m = _backend(x)
+    if m is None:
+        return _ref.dwconv2d_bn_act(x, w, scale, bias, stride, padding, act)
+    return m.dwconv2d_bn_act(x, w, scale, bias, stride, padding, code)
 
 
 def conv_plan(x_shape, w_shape, stride=1, padding=1, residual=False,
@@ -169,7 +205,10 @@ def conv1x1_chain(x, w3, s3, b3, residual, act3, w1, s1, b1, act1,
     Returns (y, a2), identical to two conv2d_bn_act calls. On GPU the
     chain kernel (csrc/chain.hip) keeps each y tile in LDS for the second
     GEMM, so y is written once and never read back. mode: 0 = policy,
-    1 = fused wherever legal, 2 = two launches; None = DEFER_CONV_CHAIN."""
+    1 = fused wherever legal, 2 = two launches; None = DEFER_CONV_CHAIN.
+    act3 and act1 are "relu" or "none"."""
+    _act_code(act3, _RELU_OR_NONE, "act3")
+    _act_code(act1, _RELU_OR_NONE, "act1")
     m = _backend(x)
     if m is None:
         y = _ref.conv2d_bn_act(x, w3, s3, b3, 1, 0, act3, residual)
@@ -205,14 +244,15 @@ def conv1x1_chain_proj(x, w3, s3, b3, xp, wp, sp, bp, act3, w1, s1, b1,
     kernel (csrc/chain.hip, PROJ) makes res per tile in registers, so res is
     neither written nor read back. Every other shape, fp32 and the CPU
     compose the two ops. mode: 0 = policy, 1 = the kernel wherever it serves
-    the shape, 2 = never; None = DEFER_CHAIN_PROJ."""
+    the shape, 2 = never; None = DEFER_CHAIN_PROJ. act3 and act1 are "relu"
+    or "none"."""
+    _act_code(act3, _RELU_OR_NONE, "act3")
+    _act_code(act1, _RELU_OR_NONE, "act1")
     if mode is None:
         mode = _CHAIN_PROJ_MODE
     if mode not in (0, 1, 2):
         raise ValueError(f"mode={mode!r}: expected 0, 1 or 2")
     if x.is_cuda and x.dtype == torch.bfloat16 and mode != 2:
-        if act3 not in ("relu", "none") or act1 not in ("relu", "none"):
-            raise ValueError("act3/act1: expected 'relu' or 'none'")
         out = _backend(x).conv1x1_chain_proj(
             x, w3, s3, b3, xp, wp, sp, bp, act3 == "relu", w1, s1, b1,
             act1 == "relu", mode, max_blocks)
@@ -244,7 +284,9 @@ def conv_bn_act_maxpool(x, w, scale, bias, stride, padding, act,
     ReLU stem followed by a 3x3/s2/p1 pool runs as one kernel
     (csrc/stem_pool.hip) that never writes the conv activation; every other
     geometry runs the two launches. mode: 0 = policy, 1 = fused wherever
-    legal, 2 = two launches; None = DEFER_STEM_POOL."""
+    legal, 2 = two launches; None = DEFER_STEM_POOL. act is "relu" or
+    "none"."""
+    _act_code(act, _RELU_OR_NONE)
     m = _backend(x)
     if m is None:
         y = _ref.conv2d_bn_act(x, w, scale, bias, stride, padding, act, None)
@@ -252,8 +294,6 @@ def conv_bn_act_maxpool(x, w, scale, bias, stride, padding, act,
     if x.dtype == torch.float32:
         y = conv2d_bn_act(x, w, scale, bias, stride, padding, act, None)
         return maxpool2d(y, pool_kernel, pool_stride, pool_padding)
-    if act not in ("relu", "none"):
-        raise ValueError(f"act={act!r}: expected 'relu' or 'none'")
     return m.conv_bn_act_maxpool(x, w, scale, bias, stride, padding,
                                  act == "relu", pool_kernel, pool_stride,
                                  pool_padding,
@@ -270,6 +310,7 @@ def stem_pool_stats():
 
 
 def batchnorm_apply(x, scale, bias, act="none"):
+    _act_code(act, _RELU_OR_NONE)
     m = _backend(x)
     if m is None:
         return _ref.batchnorm_apply(x, scale, bias, act)
@@ -277,6 +318,7 @@ def batchnorm_apply(x, scale, bias, act="none"):
 
 
 def add_act(a, b, act="relu"):
+    _act_code(act, _RELU_OR_NONE)
     m = _backend(a)
     if m is None:
         return _ref.add_act(a, b, act)
@@ -288,6 +330,14 @@ def relu(x):
     if m is None:
         return _ref.relu(x)
     return m.relu(x)
+
+
+def relu6(x):
+    """min(max(x, 0), 6), with relu's numel rules on the GPU."""
+    m = _backend(x)
+    if m is None:
+        return _ref.relu6(x)
+    return m.relu6(x)
 
 
 def maxpool2d(x, kernel=3, stride=2, padding=1):

@@ -17,6 +17,20 @@ import torch
 import torch.nn.functional as F
 
 
+def apply_act(y: torch.Tensor, act: str, known=("none", "relu", "relu6")):
+    """The activation `act` of `y`; a name outside `known` raises."""
+    if act not in known:
+        raise ValueError(f"act={act!r}: expected one of {list(known)}")
+    if act == "relu":
+        return torch.relu(y)
+    if act == "relu6":
+        return torch.clamp(y, 0.0, 6.0)
+    return y
+
+
+_RELU_ONLY = ("none", "relu")
+
+
 def conv2d_bn_act(
     x: torch.Tensor,            # [N, H, W, C]   activation
     w: torch.Tensor,            # [K, R, S, C]   weights (OHWI)
@@ -24,7 +38,7 @@ def conv2d_bn_act(
     bias: Optional[torch.Tensor],   # [K] folded BN shift / conv bias
     stride: int = 1,
     padding: int = 0,
-    act: str = "none",          # "none" | "relu"
+    act: str = "none",          # "none" | "relu" | "relu6"
     residual: Optional[torch.Tensor] = None,  # [N, OH, OW, K] added pre-act
 ) -> torch.Tensor:
     """Fused conv + (folded) batchnorm + residual-add + activation.
@@ -41,9 +55,25 @@ def conv2d_bn_act(
     y = y.permute(0, 2, 3, 1)                          # NCHW -> NHWC
     if residual is not None:
         y = y + residual.float()
-    if act == "relu":
-        y = torch.relu(y)
-    return y.to(x.dtype)
+    return apply_act(y, act).to(x.dtype)
+
+
+def dwconv2d_bn_act(x, w, scale=None, bias=None, stride=1, padding=1,
+                    act="none"):
+    """Depthwise conv + (folded) batchnorm + activation: x [N, H, W, C],
+    w [R, S, C], one filter per channel (F.conv2d with groups = C).
+
+    y[n, oh, ow, c] = act(scale[c] * sum_{r,s} x[n, oh*stride - pad + r,
+                          ow*stride - pad + s, c] * w[r, s, c] + bias[c])"""
+    c = x.shape[-1]
+    xf = x.permute(0, 3, 1, 2).float()                 # NHWC -> NCHW
+    wf = w.permute(2, 0, 1).unsqueeze(1).float()       # RSC -> [C, 1, R, S]
+    y = F.conv2d(xf, wf, bias=None, stride=stride, padding=padding, groups=c)
+    if scale is not None:
+        y = y * scale.float().view(1, -1, 1, 1)
+    if bias is not None:
+        y = y + bias.float().view(1, -1, 1, 1)
+    return apply_act(y.permute(0, 2, 3, 1), act).to(x.dtype)
 
 
 def batchnorm_apply(x, scale, bias, act="none"):
@@ -51,22 +81,22 @@ def batchnorm_apply(x, scale, bias, act="none"):
 
     scale/bias are the folded gamma/sqrt(var+eps), beta - mean*scale."""
     y = x.float() * scale.float() + bias.float()
-    if act == "relu":
-        y = torch.relu(y)
-    return y.to(x.dtype)
+    return apply_act(y, act, _RELU_ONLY).to(x.dtype)
 
 
 def add_act(a, b, act="relu"):
     """Residual add + activation (the reference's `add_N` layers +
     following ReLU — ResNet50 skip connections, test/test.py:18)."""
     y = a.float() + b.float()
-    if act == "relu":
-        y = torch.relu(y)
-    return y.to(a.dtype)
+    return apply_act(y, act, _RELU_ONLY).to(a.dtype)
 
 
 def relu(x):
     return torch.relu(x)
+
+
+def relu6(x):
+    return torch.clamp(x, 0.0, 6.0)
 
 
 def maxpool2d(x, kernel=3, stride=2, padding=1):

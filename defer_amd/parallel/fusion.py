@@ -134,6 +134,12 @@ def _is_pointwise(c: ConvBNAct) -> bool:
     return c.kernel == 1 and c.stride == 1 and c.padding == 0
 
 
+# The chain, projection and stem-pool kernels apply ReLU or nothing. A conv
+# with another activation (MobileNetV2's ReLU6) stays out of those passes;
+# fuse_residual_adds takes any, since it goes through conv2d_bn_act.
+_CHAIN_ACTS = ("relu", "none")
+
+
 def fuse_expand_reduce(graph: LayerGraph) -> LayerGraph:
     """Rewrite FusedConvAddAct(1x1) -> ConvBNAct(1x1, single input) pairs
     into one ChainedExpandReduce node plus two picks that keep the
@@ -147,10 +153,12 @@ def fuse_expand_reduce(graph: LayerGraph) -> LayerGraph:
     partner = {}                       # add_k name -> conv1 node
     for n in graph.nodes:
         if not (isinstance(n.layer, FusedConvAddAct)
-                and _is_pointwise(n.layer.conv)):
+                and _is_pointwise(n.layer.conv)
+                and n.layer.act in _CHAIN_ACTS):
             continue
         for c in consumers.get(n.name, []):
             if (isinstance(c.layer, ConvBNAct) and _is_pointwise(c.layer)
+                    and c.layer.act in _CHAIN_ACTS
                     and c.inputs == [n.name] and not c.kwargs):
                 partner[n.name] = c
                 break
@@ -274,6 +282,7 @@ def fuse_conv_pool(graph: LayerGraph) -> LayerGraph:
     partner = {}                       # conv name -> pool node
     for n in graph.nodes:
         if not (type(n.layer) is ConvBNAct and len(n.inputs) == 1
+                and n.layer.act in _CHAIN_ACTS
                 and not n.kwargs and n.name != graph.output):
             continue
         cs = consumers.get(n.name, [])

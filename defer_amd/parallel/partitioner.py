@@ -128,6 +128,12 @@ def node_times(graph: LayerGraph, input_shape=(1, 224, 224, 3),
                 t = max(f / _EFF_3X3, (in_b + out_b) / _BW_STREAM)
             else:
                 t = max(f / _EFF_1X1, (in_b + out_b) / _BW_STREAM)
+        elif isinstance(lay, L.DepthwiseConvBNAct):
+            # a VALU kernel with K = 9 or 25 and no reduction over
+            # channels: one pass over input and output at the streaming
+            # kernels' rate
+            f = float(out[0] * out[1] * out[2]) * lay.flops_per_pixel()
+            t = (in_b + out_b) / _BW_ELTW
         elif isinstance(lay, nn.Conv2d):
             # FX-imported models carry plain torch convs (NCHW):
             # out = (B, C, H, W)
