@@ -585,14 +585,39 @@ Tensor conv1x1_prebn(Tensor x, Tensor w, Tensor scale, Tensor bias,
     return out;
 }
 
+// What the chain kernel did, for tests: launches in this process, and the
+// grid and the tile height of the last one.
+struct ChainStats {
+    std::mutex mu;
+    int64_t launches = 0;
+    int64_t blocks = 0;
+    int64_t bm = 0;
+};
+ChainStats& chain_stats_ref() {
+    static ChainStats st;
+    return st;
+}
+
+py::dict conv1x1_chain_stats() {
+    auto& st = chain_stats_ref();
+    std::lock_guard<std::mutex> g(st.mu);
+    py::dict d;
+    d["launches"] = st.launches;
+    d["blocks"] = st.blocks;
+    d["bm"] = st.bm;
+    return d;
+}
+
 std::tuple<Tensor, Tensor> conv1x1_chain(
     Tensor x, Tensor w3, c10::optional<Tensor> s3, c10::optional<Tensor> b3,
     Tensor res, bool relu3, Tensor w1, c10::optional<Tensor> s1,
     c10::optional<Tensor> b1, bool relu1, int64_t mode,
-    int64_t max_blocks) {
+    int64_t max_blocks, int64_t bm) {
     // y = act3(conv1x1(x, w3)*s3+b3 + res); a2 = act1(conv1x1(y, w1)*s1+b1)
     // mode 0: fused kernel where the launcher's measured policy says so;
     // 1: fused wherever an instantiation exists; 2: always two launches.
+    // bm: rows of a fused tile, 0 = the launcher's measured policy, 64, or
+    // 128 where the class has that form (else 64).
     check_bf16(x, "x");
     check_bf16(w3, "w3");
     check_bf16(w1, "w1");
@@ -601,6 +626,7 @@ std::tuple<Tensor, Tensor> conv1x1_chain(
                 w3.size(1) == 1 && w3.size(2) == 1 && w1.size(1) == 1 &&
                 w1.size(2) == 1, "conv1x1_chain wants NHWC x, 1x1 weights");
     TORCH_CHECK(mode >= 0 && mode <= 2, "mode must be 0, 1 or 2");
+    TORCH_CHECK(bm == 0 || bm == 64 || bm == 128, "bm must be 0, 64 or 128");
     int NB = x.size(0), H = x.size(1), W = x.size(2), K1 = x.size(3);
     int N1 = w3.size(0), N2 = w1.size(0);
     TORCH_CHECK(w3.size(3) == K1 && w1.size(3) == N1, "channel mismatch");
@@ -615,15 +641,20 @@ std::tuple<Tensor, Tensor> conv1x1_chain(
     if (mode != 2 && K1 % 64 == 0 && N1 % 64 == 0 && N2 % 64 == 0) {
         auto y = at::empty({NB, H, W, N1}, x.options());
         auto a2 = at::empty({NB, H, W, N2}, x.options());
-        if (defer_hip::launch_conv1x1_chain(
-                bptr(x), bptr(w3), fptr_opt(s3, "s3", ones_buf(), N1),
-                fptr_opt(b3, "b3", zeros_buf(), N1), bptr(res),
-                bptr_mut(y), relu3, bptr(w1),
-                fptr_opt(s1, "s1", ones_buf(), N2),
-                fptr_opt(b1, "b1", zeros_buf(), N2), bptr_mut(a2), relu1,
-                (int)M, K1, N1, N2, mode == 1, (int)max_blocks,
-                cur_stream()))
+        defer_hip::ChainLaunch l = defer_hip::launch_conv1x1_chain(
+            bptr(x), bptr(w3), fptr_opt(s3, "s3", ones_buf(), N1),
+            fptr_opt(b3, "b3", zeros_buf(), N1), bptr(res), bptr_mut(y),
+            relu3, bptr(w1), fptr_opt(s1, "s1", ones_buf(), N2),
+            fptr_opt(b1, "b1", zeros_buf(), N2), bptr_mut(a2), relu1, (int)M,
+            K1, N1, N2, mode == 1, (int)max_blocks, (int)bm, cur_stream());
+        if (l.blocks > 0) {
+            auto& st = chain_stats_ref();
+            std::lock_guard<std::mutex> g(st.mu);
+            ++st.launches;
+            st.blocks = l.blocks;
+            st.bm = l.bm;
             return {y, a2};
+        }
     }
     auto y = conv2d_bn_act(x, w3, s3, b3, res, 1, 0, relu3);
     auto a2 = conv2d_bn_act(y, w1, s1, b1, c10::nullopt, 1, 0, relu1);
@@ -1367,7 +1398,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("conv1x1_chain", &conv1x1_chain, py::arg("x"), py::arg("w3"),
           py::arg("s3"), py::arg("b3"), py::arg("res"), py::arg("relu3"),
           py::arg("w1"), py::arg("s1"), py::arg("b1"), py::arg("relu1"),
-          py::arg("mode") = 0, py::arg("max_blocks") = 0);
+          py::arg("mode") = 0, py::arg("max_blocks") = 0, py::arg("bm") = 0);
+    m.def("conv1x1_chain_stats", &conv1x1_chain_stats);
     m.def("conv1x1_chain_proj", &conv1x1_chain_proj, py::arg("x"),
           py::arg("w3"), py::arg("s3"), py::arg("b3"), py::arg("xp"),
           py::arg("wp"), py::arg("sp"), py::arg("bp"), py::arg("relu3"),

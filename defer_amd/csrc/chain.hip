@@ -29,7 +29,10 @@
 // EIGHT waves, so that every SIMD still holds two (NW = 8, "DEEP" below):
 // GEMM1 and GEMM2 split 2 x 4 over the waves, epilogue 1 is one 64-row
 // round that all eight waves write (16 KiB bounce), and the barrier
-// after GEMM1 is folded into the bounce's own, three per chunk.
+// after GEMM1 is folded into the bounce's own, three per chunk. Where the
+// K1 = 256, N2 = 256 class has more than one round of 64-row tiles per CU it
+// runs 128-row tiles instead (BM = 128, chain_tile128 below), which stage
+// the weights half as often per row.
 //
 // Loads are issued ahead of their use: the residual chunk RES(j+1) — the
 // HBM-bound stream — right after the W1(j) stage, a whole chunk early
@@ -76,7 +79,337 @@ __device__ __forceinline__ void ch_glds16(const bf16* src, bf16* lds_base) {
         16, 0, 0);
 }
 
-template <int K1, int N2, int NW, int WPS, bool PROJ = false>
+// The 128-row tile of the K1 = 256 classes (eight waves, one block per CU).
+// A chunk stages the same 64 KiB of W3 and W1 as the 64-row tile does, for
+// twice the rows, so the weight stream through LDS per output row is halved.
+//   - waves are 4 row slabs of 32 x 2 across n: GEMM1 32 x 32 per wave and
+//     chunk, GEMM2 32 x N2/2;
+//   - the A panel [128 x K1] is staged to LDS once per tile like the 64-row
+//     one; the next tile's is issued with W3(0) in the last chunk, under its
+//     GEMM2 (the panel is free once every wave is past the last GEMM1).
+//     Held in registers instead (64 a lane, loaded in the GEMM1 mapping as
+//     PROJ's XP is) it did not fit: with acc2 (64), acc1 and the look-ahead
+//     sets the kernel needed 256 registers and spilled 10 to 15, and the
+//     reloads, which count on vmcnt, drained the W1 stage inside GEMM1;
+//   - epilogue 1 is two 64-row rounds through the 16 KiB bounce (two
+//     residual loads a thread stay in flight, vmcnt(2)); epilogue 2 is two
+//     64-row rounds through the bounce and the y-tile (32 KiB, rows of N2
+//     bf16 with the 16-B chunk index XORed by the row group, in place of
+//     the padded stride that would not fit), clear of both weight slices.
+// LDS: A panel 64 KiB + W3 chunk 32 KiB + W1 slice 32 KiB + bounce 16 KiB +
+// y-tile 16 KiB = 160 KiB, all a CU has: no second weight slice. Fragment
+// mapping, accumulation order (k ascending; j, then k) and epilogue
+// expressions are the 64-row tile's: both outputs are bit-identical to it
+// and to the two launches (tests/test_conv_chain_bm128_gpu.py).
+template <int K1, int N2>
+__device__ __forceinline__ void chain_tile128(
+    const bf16* __restrict__ X, const bf16* __restrict__ W3,
+    const float* __restrict__ S3, const float* __restrict__ B3,
+    const bf16* __restrict__ RES, bf16* __restrict__ Y,
+    const bf16* __restrict__ W1, const float* __restrict__ S1,
+    const float* __restrict__ B1, bf16* __restrict__ A2,
+    int M, int N1, int act3, int act1) {
+    constexpr int BM = 128;
+    constexpr int TPB = 8 * WAVE;
+    constexpr int NK1 = K1 / 64;             // k-tiles of the W3 chunk
+    constexpr int NT2 = N2 / 64;             // 64-row tiles of the W1 slice
+    constexpr int WN2 = N2 / 2;              // GEMM2 wave n-width
+    constexpr int NI2 = WN2 / 16;
+    constexpr int ER = 64;                   // rows per epilogue round
+    constexpr int NR = BM / ER;
+    constexpr int SCR = ER * 64 * 2;         // fp32 bounce, in bf16 units
+    constexpr int YT = BM * 64;              // y-tile, bf16 units
+    static_assert(ER * N2 <= SCR + YT, "out-bounce fits");
+    static_assert(N2 * 8 % TPB == 0, "whole out-bounce chunks per thread");
+
+    __shared__ __attribute__((aligned(16)))
+    bf16 lds[BM * K1 + 64 * K1 + N2 * 64 + SCR + YT];
+    static_assert(sizeof(lds) <= 163840, "one block's LDS");
+    bf16* Ap = lds;                          // NK1 tiles [128][64]
+    bf16* W3b = Ap + BM * K1;                // NK1 tiles [64 n][64 k]
+    bf16* W1b = W3b + 64 * K1;               // NT2 tiles [64 n][64 k]
+    float* scratch = (float*)(W1b + N2 * 64);
+    bf16* ytile = W1b + N2 * 64 + SCR;       // [128][64]
+    bf16* obuf = (bf16*)scratch;             // epilogue 2: scratch + ytile
+
+    const int tid = threadIdx.x;
+    const int wave = tid / WAVE;
+    const int lane = tid % WAVE;
+    const int wm = wave >> 1;                // 32-row slab, 0..3
+    const int wn = wave & 1;
+    const int lo16 = lane & 15;
+    const int hi4 = lane >> 4;
+    const int mtiles = (M + BM - 1) / BM;
+    const int NJ = N1 / 64;
+
+    // staging geometry of one [64][64] tile: one 16-B chunk per thread
+    const int t_row = tid / 8;
+    const int t_k8 = ch_swz(t_row, tid % 8);
+    auto stage_w3 = [&](int j) {
+        const bf16* src = W3 + (long)(j * 64 + t_row) * K1 + t_k8 * 8;
+#pragma unroll
+        for (int kt = 0; kt < NK1; ++kt)
+            ch_glds16(src + kt * 64, W3b + kt * 4096 + wave * 64 * 8);
+    };
+    auto stage_w1 = [&](int j) {
+        const bf16* src = W1 + (long)t_row * N1 + j * 64 + t_k8 * 8;
+#pragma unroll
+        for (int t = 0; t < NT2; ++t)
+            ch_glds16(src + (long)t * 64 * N1,
+                      W1b + t * 4096 + wave * 64 * 8);
+    };
+    // the panel's k-tiles are two such tiles high: rows t_row and t_row + 64
+    // (the same swizzle: 64 keeps row & 7)
+    auto stage_a = [&](int mt) {
+#pragma unroll
+        for (int i = 0; i < BM / 64; ++i) {
+            int m = mt * BM + i * 64 + t_row;
+            if (m >= M) m = M - 1;           // clamped rows are never stored
+            const bf16* src = X + (long)m * K1 + t_k8 * 8;
+#pragma unroll
+            for (int kt = 0; kt < NK1; ++kt)
+                ch_glds16(src + kt * 64,
+                          Ap + kt * (BM * 64) + i * 4096 + wave * 64 * 8);
+        }
+    };
+
+    // epilogue chunk geometry: one 8-column chunk per thread per round
+    const int e_rl = tid >> 3;               // round-local row 0..63
+    const int e_c8 = (tid & 7) * 8;
+    const int e_cs = e_c8 ^ (((e_rl >> 2) & 3) << 4);
+
+    int mt = blockIdx.x;
+    if (mt >= mtiles) return;
+    stage_a(mt);
+    stage_w3(0);
+    float sc3n[2], bi3n[2];
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+        int n = wn * 32 + ni * 16 + lo16;
+        sc3n[ni] = S3[n];
+        bi3n[ni] = B3[n];
+    }
+    auto res_load = [&](bf16x8* rv, int m0, int j) {
+#pragma unroll
+        for (int h = 0; h < NR; ++h) {
+            int m = m0 + h * ER + e_rl;
+            if (m >= M) m = M - 1;
+            rv[h] = load_bf16x8(RES + (long)m * N1 + j * 64 + e_c8);
+        }
+    };
+    bf16x8 rvn[NR];
+    res_load(rvn, mt * BM, 0);
+
+    for (; mt < mtiles; mt += gridDim.x) {
+        const int m0 = mt * BM;
+        const bool more = mt + (int)gridDim.x < mtiles;
+        f32x4 acc2[2][NI2];
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < NI2; ++ni)
+                acc2[mi][ni] = {0.f, 0.f, 0.f, 0.f};
+
+        for (int j = 0; j < NJ; ++j) {
+            // A panel, W3(j) and the look-ahead registers landed;
+            // every wave is past GEMM2(j-1) (or the previous tile's
+            // out-bounce), so W1b, the bounce and the y-tile are free
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            const int jn = j + 1 < NJ ? j + 1 : 0;
+            // look-ahead registers handed over by explicit moves here,
+            // where nothing is in flight (see the 64-row tile's DEEP)
+            bf16x8 rv[NR];
+#pragma unroll
+            for (int h = 0; h < NR; ++h) {
+                u32x4 t = __builtin_bit_cast(u32x4, rvn[h]), c;
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    asm volatile("v_mov_b32 %0, %1"
+                                 : "=v"(c[q]) : "v"(t[q]) : "memory");
+                rv[h] = __builtin_bit_cast(bf16x8, c);
+            }
+            float sc3[2], bi3[2];
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) {
+                asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3"
+                             : "=&v"(sc3[ni]), "=&v"(bi3[ni])
+                             : "v"(sc3n[ni]), "v"(bi3n[ni]) : "memory");
+                int n = jn * 64 + wn * 32 + ni * 16 + lo16;
+                sc3n[ni] = S3[n];
+                bi3n[ni] = B3[n];
+            }
+            stage_w1(j);
+            // exactly NR loads, unconditionally, AFTER the W1 stage: the
+            // counted wait in front of epilogue 1 lets them stay in flight
+            res_load(rvn, (j + 1 < NJ || !more)
+                              ? m0 : m0 + (int)gridDim.x * BM, jn);
+            // hipcc would sink the stage into the middle of GEMM1 and the
+            // residual loads to its end, and halve the cover of both
+            __builtin_amdgcn_sched_barrier(0);
+
+            // ---- GEMM1: acc1[128x64] = Apanel @ W3_j^T (igemm mapping)
+            f32x4 acc1[2][2];
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni)
+                    acc1[mi][ni] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kt = 0; kt < NK1; ++kt)
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    bf16x8 af[2], bfr[2];
+#pragma unroll
+                    for (int mi = 0; mi < 2; ++mi) {
+                        int row = wm * 32 + mi * 16 + lo16;
+                        af[mi] = *reinterpret_cast<bf16x8*>(
+                            Ap + kt * (BM * 64) + row * 64
+                               + ch_swz(row, ks * 4 + hi4) * 8);
+                    }
+#pragma unroll
+                    for (int ni = 0; ni < 2; ++ni) {
+                        int row = wn * 32 + ni * 16 + lo16;
+                        bfr[ni] = *reinterpret_cast<bf16x8*>(
+                            W3b + kt * 4096 + row * 64
+                                + ch_swz(row, ks * 4 + hi4) * 8);
+                    }
+#pragma unroll
+                    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                        for (int ni = 0; ni < 2; ++ni)
+                            acc1[mi][ni] = MFMA_BF16_16x16x32(
+                                af[mi], bfr[ni], acc1[mi][ni]);
+                }
+            // W1(j) landed; only the NR residual loads issued after it may
+            // stay in flight. The bounce's own barrier publishes W1(j)
+            asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
+            static_assert(NR == 2, "the counted wait leaves NR loads");
+
+            // ---- epilogue 1: two rounds of 64 rows through the fp32
+            // bounce; the four waves whose slabs lie in the round write it
+#pragma unroll
+            for (int h = 0; h < NR; ++h) {
+                if (wm * 32 / ER == h) {
+#pragma unroll
+                    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                int rl = wm * 32 % ER + mi * 16 + hi4 * 4 + e;
+                                int c = wn * 32 + ni * 16 + lo16;
+                                int cs = c ^ (((rl >> 2) & 3) << 4);
+                                scratch[rl * 64 + cs] =
+                                    acc1[mi][ni][e] * sc3[ni] + bi3[ni];
+                            }
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                f32x4 v0 = *reinterpret_cast<f32x4*>(
+                    scratch + e_rl * 64 + e_cs);
+                f32x4 v1 = *reinterpret_cast<f32x4*>(
+                    scratch + e_rl * 64 + e_cs + 4);
+                bf16x8 o;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    float v = q < 4 ? v0[q] : v1[q - 4];
+                    v += bf2f(rv[h][q]);
+                    o[q] = f2bf(apply_act(v, act3));
+                }
+                const int r = h * ER + e_rl;
+                if (m0 + r < M)
+                    store_bf16x8(Y + (long)(m0 + r) * N1 + j * 64 + e_c8, o);
+                // same 8 columns = one 16-B chunk of the A-operand layout
+                store_bf16x8(ytile + r * 64 + ch_swz(r, tid & 7) * 8, o);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+            }
+            // next chunk's W3 (wraps to W3(0) of the next tile), after the
+            // chunk's last LDS write, and in the last chunk the next tile's
+            // A panel: every wave is past its last GEMM1. GEMM2 (LDS reads
+            // only) is their latency cover
+            if (j + 1 < NJ || more) stage_w3(jn);
+            if (j + 1 == NJ && more) stage_a(mt + (int)gridDim.x);
+
+            // ---- GEMM2: acc2[128 x N2] += ytile @ W1_j^T
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                bf16x8 af[2];
+#pragma unroll
+                for (int mi = 0; mi < 2; ++mi) {
+                    int row = wm * 32 + mi * 16 + lo16;
+                    af[mi] = *reinterpret_cast<bf16x8*>(
+                        ytile + row * 64 + ch_swz(row, ks * 4 + hi4) * 8);
+                }
+#pragma unroll
+                for (int ni = 0; ni < NI2; ++ni) {
+                    int row = wn * WN2 + ni * 16 + lo16;
+                    bf16x8 bfr = *reinterpret_cast<bf16x8*>(
+                        W1b + row * 64 + ch_swz(row, ks * 4 + hi4) * 8);
+#pragma unroll
+                    for (int mi = 0; mi < 2; ++mi)
+                        acc2[mi][ni] = MFMA_BF16_16x16x32(af[mi], bfr,
+                                                          acc2[mi][ni]);
+                }
+            }
+        }
+
+        // ---- epilogue 2: s1/b1 + act1 on the accumulator, two rounds of
+        // 64 rows through a bf16 bounce (the four row groups a wave writes
+        // at once land 8 banks apart). s1/b1 are read here, once a tile,
+        // and not held across the chunks
+        float sc1[NI2], bi1[NI2];
+#pragma unroll
+        for (int ni = 0; ni < NI2; ++ni) {
+            int n = wn * WN2 + ni * 16 + lo16;
+            sc1[ni] = S1[n];
+            bi1[ni] = B1[n];
+        }
+#pragma unroll
+        for (int h = 0; h < NR; ++h) {
+            // h = 0: every wave is past GEMM2, the bounce and the y-tile
+            // are free; h = 1: round 0 has been read
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            if (wm * 32 / ER == h) {
+#pragma unroll
+                for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                    for (int ni = 0; ni < NI2; ++ni)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            int r = wm * 32 % ER + mi * 16 + hi4 * 4 + e;
+                            int c = wn * WN2 + ni * 16 + lo16;
+                            int cs = c ^ (((r >> 2) & 3) << 4);
+                            float v = acc2[mi][ni][e] * sc1[ni] + bi1[ni];
+                            obuf[r * N2 + cs] = f2bf(apply_act(v, act1));
+                        }
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+#pragma unroll
+            for (int i = 0; i < N2 * 8 / TPB; ++i) {
+                int chunk = tid + i * TPB;
+                int r = chunk / (N2 / 8);
+                int c8 = (chunk % (N2 / 8)) * 8;
+                bf16x8 o = load_bf16x8(
+                    obuf + r * N2 + (c8 ^ (((r >> 2) & 3) << 4)));
+                if (m0 + h * ER + r < M)
+                    store_bf16x8(A2 + (long)(m0 + h * ER + r) * N2 + c8, o);
+            }
+        }
+        // the next chunk's top barrier orders these reads before the bounce
+        // is written again
+    }
+    // no LDS DMA may outlive the block (the last chunk stages nothing;
+    // this documents the invariant)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// BM = 128 (K1 = 256, eight waves) is chain_tile128 above; everything below
+// is the 64-row tile
+template <int K1, int N2, int NW, int WPS, bool PROJ = false, int BM = CH_BM>
 __global__ __launch_bounds__(NW * WAVE, WPS) void conv1x1_chain_kernel(
     const bf16* __restrict__ X,      // [M][K1]
     const bf16* __restrict__ W3,     // [N1][K1]
@@ -93,6 +426,13 @@ __global__ __launch_bounds__(NW * WAVE, WPS) void conv1x1_chain_kernel(
     const float* __restrict__ SP,    // PROJ: [N1]
     const float* __restrict__ BP,    // PROJ: [N1]
     int M, int N1, int act3, int act1) {
+    static_assert(BM == CH_BM || (BM == 128 && NW == 8 && !PROJ),
+                  "128-row tiles are built for eight waves, no projection");
+    if constexpr (BM == 128) {
+        chain_tile128<K1, N2>(X, W3, S3, B3, RES, Y, W1, S1, B1, A2, M, N1,
+                              act3, act1);
+        return;
+    }
     constexpr int TPB = NW * WAVE;
     constexpr bool DEEP = NW == 8;           // two waves per SIMD, one block
     constexpr int WNS = NW / 2;              // waves across n (2 row slabs)
@@ -562,19 +902,48 @@ bool chain_policy(int K1, int N1, int N2) {
     return false;
 }
 
+// Tile height of the K1 = 256, N2 = 256 instantiation: 128 rows where they
+// measured faster than 64 (tools/chainbench.py --bm, MI355X, N1 = 1024, us,
+// min..max of 2 x 3 repeats; 128 rows | 64 rows | 64-row tiles):
+//   batch 256   91.3..95.0 | 116.2..127.5 | 784
+//   batch 128   46.8..48.1 |  57.2..57.7  | 392
+//   batch 64    44.8..46.5 |  30.5..31.0  | 196 (98 blocks on 256 CUs)
+// The gate is the 64-row tile count: above 256 the 64-row form runs more
+// than one round of tiles per CU, at and below it 128 rows would leave CUs
+// without a tile.
+bool bm128_policy(int M) { return (M + CH_BM - 1) / CH_BM > 256; }
+
 }  // namespace
 
-bool launch_conv1x1_chain(const void* x, const void* w3, const float* s3,
-                          const float* b3, const void* res, void* y,
-                          bool relu3, const void* w1, const float* s1,
-                          const float* b1, void* a2, bool relu1, int M,
-                          int K1, int N1, int N2, bool force,
-                          int max_blocks, hipStream_t s) {
-    if (M <= 0 || N1 < 64 || N1 % 64 != 0) return false;
-    if (!force && !chain_policy(K1, N1, N2)) return false;
-    const int mtiles = (M + CH_BM - 1) / CH_BM;
+ChainLaunch launch_conv1x1_chain(const void* x, const void* w3,
+                                 const float* s3, const float* b3,
+                                 const void* res, void* y, bool relu3,
+                                 const void* w1, const float* s1,
+                                 const float* b1, void* a2, bool relu1,
+                                 int M, int K1, int N1, int N2, bool force,
+                                 int max_blocks, int bm, hipStream_t s) {
+    if (M <= 0 || N1 < 64 || N1 % 64 != 0) return {0, 0};
+    if (!force && !chain_policy(K1, N1, N2)) return {0, 0};
     const int a3 = relu3 ? ACT_RELU : ACT_NONE;
     const int a1 = relu1 ? ACT_RELU : ACT_NONE;
+    if (K1 == 256 && N2 == 256 && (bm == 128 || (bm == 0 && bm128_policy(M)))) {
+        const int mtiles = (M + 127) / 128;
+        int gx = 256;
+        if (max_blocks > 0) gx = max_blocks;
+        if (gx > mtiles) gx = mtiles;
+        if (max_blocks <= 0) {               // even rounds, as below
+            int rounds = (mtiles + gx - 1) / gx;
+            gx = (mtiles + rounds - 1) / rounds;
+        }
+        hipLaunchKernelGGL(
+            (conv1x1_chain_kernel<256, 256, 8, 1, false, 128>), dim3(gx),
+            dim3(8 * WAVE), 0, s, (const bf16*)x, (const bf16*)w3, s3, b3,
+            (const bf16*)res, (bf16*)y, (const bf16*)w1, s1, b1, (bf16*)a2,
+            (const bf16*)nullptr, (const bf16*)nullptr,
+            (const float*)nullptr, (const float*)nullptr, M, N1, a3, a1);
+        return {gx, 128};
+    }
+    const int mtiles = (M + CH_BM - 1) / CH_BM;
 #define CHAIN(K1v, N2v, NWv, WPSv)                                        \
     do {                                                                  \
         int gx = 256 * WPSv;                                              \
@@ -594,7 +963,7 @@ bool launch_conv1x1_chain(const void* x, const void* w3, const float* s3,
                            s1, b1, (bf16*)a2, (const bf16*)nullptr,       \
                            (const bf16*)nullptr, (const float*)nullptr,   \
                            (const float*)nullptr, M, N1, a3, a1);         \
-        return true;                                                      \
+        return {gx, CH_BM};                                               \
     } while (0)
     if (K1 == 64 && N2 == 64) CHAIN(64, 64, 4, 3);
     if (K1 == 64 && N2 == 128) CHAIN(64, 128, 4, 3);
@@ -603,7 +972,7 @@ bool launch_conv1x1_chain(const void* x, const void* w3, const float* s3,
     if (K1 == 256 && N2 == 256) CHAIN(256, 256, 8, 1);
     if (K1 == 256 && N2 == 512) CHAIN(256, 512, 8, 1);
 #undef CHAIN
-    return false;
+    return {0, 0};
 }
 
 int launch_conv1x1_chain_proj(const void* x, const void* w3, const float* s3,

@@ -52,16 +52,20 @@ void launch_gemm_prebn(const void* x, const void* w, const float* ps,
 //   y  = act3((x[M,K1] @ w3[N1,K1]^T) * s3 + b3 + res[M,N1])
 //   a2 = act1((y @ w1[N2,N1]^T) * s1 + b1)
 // both bit-identical to two GEMM-mode launch_conv_igemm calls. Returns
-// false (nothing launched) when the shape has no instantiation or, with
-// force == false, is not in the measured-win policy table. max_blocks
-// caps the grid (0 = policy) so small M can exercise several m-tiles
-// per block.
-bool launch_conv1x1_chain(const void* x, const void* w3, const float* s3,
-                          const float* b3, const void* res, void* y,
-                          bool relu3, const void* w1, const float* s1,
-                          const float* b1, void* a2, bool relu1, int M,
-                          int K1, int N1, int N2, bool force,
-                          int max_blocks, hipStream_t s);
+// the grid and the tile height it launched, blocks == 0 (nothing launched)
+// when the shape has no instantiation or, with force == false, is not in
+// the measured-win policy table. max_blocks caps the grid (0 = policy) so
+// small M can exercise several m-tiles per block. bm picks the rows of a
+// tile: 0 = the measured policy, 64, or 128 (served for K1 = N2 = 256;
+// every other class runs 64 rows whatever bm says).
+struct ChainLaunch { int blocks, bm; };
+ChainLaunch launch_conv1x1_chain(const void* x, const void* w3,
+                                 const float* s3, const float* b3,
+                                 const void* res, void* y, bool relu3,
+                                 const void* w1, const float* s1,
+                                 const float* b1, void* a2, bool relu1,
+                                 int M, int K1, int N1, int N2, bool force,
+                                 int max_blocks, int bm, hipStream_t s);
 // the same pair with a projected residual made inside the kernel:
 //   res = bf16((xp[M,KP] @ wp[N1,KP]^T) * sp + bp)
 // in place of a res tensor; bit-identical to a GEMM-mode launch_conv_igemm

@@ -194,9 +194,18 @@ def conv1x1_prebn(x, w, scale, bias, out_scale=None, out_bias=None):
 # two launches, "force" = fused wherever an instantiation exists.
 _CHAIN_MODE = _env_mode("DEFER_CONV_CHAIN")
 
+# A/B switch for the 128-row tile of the chain kernel (same convention):
+# unset = the launcher's measured policy, "0" = never, "force" = wherever a
+# class has that form. As the bm argument of conv1x1_chain: 0, 64, 128.
+def _env_chain_bm():
+    return {0: 0, 1: 128, 2: 64}[_env_mode("DEFER_CHAIN_BM128")]
+
+
+_CHAIN_BM = _env_chain_bm()
+
 
 def conv1x1_chain(x, w3, s3, b3, residual, act3, w1, s1, b1, act1,
-                  mode=None, max_blocks=0):
+                  mode=None, max_blocks=0, bm=None):
     """Bottleneck boundary pair in one call:
 
         y  = act3(conv1x1(x, w3)*s3 + b3 + residual)
@@ -206,9 +215,16 @@ def conv1x1_chain(x, w3, s3, b3, residual, act3, w1, s1, b1, act1,
     chain kernel (csrc/chain.hip) keeps each y tile in LDS for the second
     GEMM, so y is written once and never read back. mode: 0 = policy,
     1 = fused wherever legal, 2 = two launches; None = DEFER_CONV_CHAIN.
+    bm: rows of a fused tile, 0 = the launcher's measured policy, 64, or 128
+    (only the 256-channel x, 256-channel a2 class has a 128-row form; every
+    other class runs 64 rows whatever bm says); None = DEFER_CHAIN_BM128.
     act3 and act1 are "relu" or "none"."""
     _act_code(act3, _RELU_OR_NONE, "act3")
     _act_code(act1, _RELU_OR_NONE, "act1")
+    if bm is None:
+        bm = _CHAIN_BM
+    if bm not in (0, 64, 128):
+        raise ValueError(f"bm={bm!r}: expected 0, 64 or 128")
     m = _backend(x)
     if m is None:
         y = _ref.conv2d_bn_act(x, w3, s3, b3, 1, 0, act3, residual)
@@ -220,7 +236,16 @@ def conv1x1_chain(x, w3, s3, b3, residual, act3, w1, s1, b1, act1,
         return y, a2
     return m.conv1x1_chain(x, w3, s3, b3, residual, act3 == "relu", w1, s1,
                            b1, act1 == "relu",
-                           _CHAIN_MODE if mode is None else mode, max_blocks)
+                           _CHAIN_MODE if mode is None else mode, max_blocks,
+                           bm)
+
+
+def conv1x1_chain_stats():
+    """What the fused kernel of conv1x1_chain did in this process:
+    {"launches": its launches so far, "blocks", "bm": the grid and the rows
+    per tile of the last one}. Lets tests tell the 64-row and the 128-row
+    form apart, whose results are identical by design."""
+    return _stats("conv1x1_chain_stats")
 
 
 # A/B switch for the chain kernel that makes the projection shortcut itself

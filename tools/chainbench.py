@@ -36,22 +36,22 @@ PAIR_CLASSES = [
 ]
 
 
-def time_mode(args, mode, iters, max_blocks=0):
+def time_mode(args, mode, iters, max_blocks=0, bm=None):
     for _ in range(5):
-        ops.conv1x1_chain(*args, mode=mode, max_blocks=max_blocks)
+        ops.conv1x1_chain(*args, mode=mode, max_blocks=max_blocks, bm=bm)
     torch.cuda.synchronize()
     t0 = torch.cuda.Event(True)
     t1 = torch.cuda.Event(True)
     t0.record()
     for _ in range(iters):
-        ops.conv1x1_chain(*args, mode=mode, max_blocks=max_blocks)
+        ops.conv1x1_chain(*args, mode=mode, max_blocks=max_blocks, bm=bm)
     t1.record()
     torch.cuda.synchronize()
     return t0.elapsed_time(t1) * 1e3 / iters
 
 
 def bench_class(name, HW, K1, N1, N2, count, B, iters, repeats,
-                max_blocks=0, fused_only=False):
+                max_blocks=0, fused_only=False, bm=None):
     dev = "cuda:0"
     bf = torch.bfloat16
     x = torch.randn(B, HW, HW, K1, device=dev, dtype=bf)
@@ -63,20 +63,21 @@ def bench_class(name, HW, K1, N1, N2, count, B, iters, repeats,
     s1 = torch.rand(N2, device=dev) + 0.5
     b1 = torch.randn(N2, device=dev) * 0.1
     args = (x, w3, s3, b3, res, "relu", w1, s1, b1, "relu")
-    y1, a1 = ops.conv1x1_chain(*args, mode=1, max_blocks=max_blocks)
+    y1, a1 = ops.conv1x1_chain(*args, mode=1, max_blocks=max_blocks, bm=bm)
+    tile = ops.conv1x1_chain_stats()["bm"]
     y2, a2 = ops.conv1x1_chain(*args, mode=2)
     same = bool(torch.equal(y1, y2) and torch.equal(a1, a2))
     # alternate the modes so drift hits both alike
     fused, two = [], []
     for _ in range(repeats):
-        fused.append(time_mode(args, 1, iters, max_blocks))
+        fused.append(time_mode(args, 1, iters, max_blocks, bm))
         if not fused_only:
             two.append(time_mode(args, 2, iters))
     M = B * HW * HW
     # bytes the fused kernel must move: x, res in; y, a2 out
     gb = M * (K1 + 2 * N1 + N2) * 2 / 1e9
     return dict(name=name, batch=B, M=M, pairs=count, bitwise=same,
-                max_blocks=max_blocks,
+                max_blocks=max_blocks, tile_rows=tile,
                 fused_us=[round(v, 1) for v in fused],
                 two_us=[round(v, 1) for v in two],
                 fused_tbps=round(gb / (min(fused) * 1e-6) / 1e3, 2))
@@ -148,6 +149,11 @@ def main():
     ap.add_argument("--max-blocks", type=int, nargs="+", default=[0],
                     help="persistent-grid caps to time the fused kernel at "
                          "(0 = the launcher's own grid)")
+    ap.add_argument("--bm", type=int, nargs="+", default=[None],
+                    choices=[0, 64, 128],
+                    help="rows of a fused tile to time (0 = the launcher's "
+                         "policy; default: DEFER_CHAIN_BM128); the projected "
+                         "class has one form and ignores it")
     ap.add_argument("--fused-only", action="store_true",
                     help="time only the fused kernel (counter runs: one "
                          "kernel name in the profile)")
@@ -157,14 +163,20 @@ def main():
                or any(k in c[0] for k in args.classes)]
     rows = []
     for B in args.batches:
-        for c, mb in [(c, mb) for c in classes for mb in args.max_blocks]:
-            bench = bench_proj if c is PROJ_CLASS else bench_class
-            r = bench(*c, B, args.iters, args.repeats, mb, args.fused_only)
+        for c, mb, bm in [(c, mb, bm) for c in classes
+                          for mb in args.max_blocks for bm in args.bm]:
+            if c is PROJ_CLASS:
+                r = bench_proj(*c, B, args.iters, args.repeats, mb,
+                               args.fused_only)
+            else:
+                r = bench_class(*c, B, args.iters, args.repeats, mb,
+                                args.fused_only, bm)
             rows.append(r)
             f, t = r["fused_us"], r["two_us"] or [float("nan")]
             verdict = ("WIN" if max(f) < min(t)
                        else "loss" if min(f) > max(t) else "noise")
             print(f"b{B:<4d} {r['name']:18s} M={r['M']:7d} mb={mb:<4d}"
+                  f"bm={r.get('tile_rows', 64):<4d}"
                   f"fused {min(f):7.1f}..{max(f):7.1f} us  "
                   f"two {min(t):7.1f}..{max(t):7.1f} us  "
                   f"{r['fused_tbps']:5.2f} TB/s  bitwise={r['bitwise']}  "
