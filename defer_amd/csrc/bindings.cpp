@@ -54,6 +54,23 @@ void check_f32(const Tensor& t, const char* name) {
 
 const float* f32ptr(const Tensor& t) { return t.data_ptr<float>(); }
 
+// The pooling geometry both dtypes accept, which is what F.max_pool2d
+// accepts: a stride of 0 would divide by zero below, and with
+// pad > kernel / 2 a border window has no tap.
+void check_pool(const Tensor& x, int64_t kernel, int64_t stride,
+                int64_t pad, const char* op) {
+    TORCH_CHECK(x.dim() == 4, "x must be NHWC");
+    TORCH_CHECK(kernel >= 1, op, ": kernel must be >= 1, got ", kernel);
+    TORCH_CHECK(stride >= 1, op, ": stride must be >= 1, got ", stride);
+    TORCH_CHECK(pad >= 0 && pad <= kernel / 2, op,
+                ": pad must be in [0, kernel / 2], got pad ", pad,
+                " for kernel ", kernel);
+    TORCH_CHECK(x.size(1) + 2 * pad >= kernel &&
+                x.size(2) + 2 * pad >= kernel, op, ": input ", x.size(1),
+                "x", x.size(2), " with pad ", pad,
+                " is smaller than the window ", kernel);
+}
+
 // activation codes of the ops that know ReLU6 (ACT_* of csrc/common.h);
 // C++ callers that pass a bool get none / relu
 enum { kActNone = 0, kActRelu = 1, kActRelu6 = 2 };
@@ -756,6 +773,9 @@ Tensor bn_act(Tensor x, Tensor scale, Tensor bias, bool relu) {
     check_bf16(x, "x");
     int C = x.size(-1);
     TORCH_CHECK(C % 8 == 0, "C must be a multiple of 8");
+    TORCH_CHECK(scale.is_cuda() && bias.is_cuda() &&
+                scale.numel() == C && bias.numel() == C,
+                "scale/bias must be GPU tensors of length C");
     auto out = at::empty_like(x);
     auto sf = scale.to(at::kFloat).contiguous();
     auto bf = bias.to(at::kFloat).contiguous();
@@ -906,6 +926,7 @@ Tensor softmax(Tensor x) {
         return out;
     }
     check_bf16(x, "x");
+    TORCH_CHECK(x.dim() >= 1 && x.numel() > 0, "softmax of nothing");
     int cols = x.size(-1);
     long rows = x.numel() / cols;
     auto out = at::empty_like(x);
@@ -917,7 +938,7 @@ Tensor softmax(Tensor x) {
 Tensor maxpool2d(Tensor x, int64_t kernel, int64_t stride, int64_t pad) {
     if (is_f32(x, "x")) {
         check_f32(x, "x");
-        TORCH_CHECK(x.dim() == 4, "x must be NHWC");
+        check_pool(x, kernel, stride, pad, "maxpool2d");
         int NB = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
         TORCH_CHECK(C % 4 == 0, "fp32 maxpool2d needs C % 4 == 0, got ", C);
         int OH = (int)((H + 2 * pad - kernel) / stride + 1);
@@ -929,7 +950,7 @@ Tensor maxpool2d(Tensor x, int64_t kernel, int64_t stride, int64_t pad) {
         return out;
     }
     check_bf16(x, "x");
-    TORCH_CHECK(x.dim() == 4, "x must be NHWC");
+    check_pool(x, kernel, stride, pad, "maxpool2d");
     int NB = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
     TORCH_CHECK(C % 8 == 0, "C must be a multiple of 8");
     int OH = (int)((H + 2 * pad - kernel) / stride + 1);
@@ -1032,7 +1053,7 @@ Tensor conv_bn_act_maxpool(Tensor x, Tensor w, c10::optional<Tensor> scale,
 Tensor avgpool2d(Tensor x, int64_t kernel, int64_t stride, int64_t pad) {
     if (is_f32(x, "x")) {
         check_f32(x, "x");
-        TORCH_CHECK(x.dim() == 4, "x must be NHWC");
+        check_pool(x, kernel, stride, pad, "avgpool2d");
         int NB = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
         TORCH_CHECK(C % 4 == 0, "fp32 avgpool2d needs C % 4 == 0, got ", C);
         int OH = (int)((H + 2 * pad - kernel) / stride + 1);
@@ -1044,7 +1065,7 @@ Tensor avgpool2d(Tensor x, int64_t kernel, int64_t stride, int64_t pad) {
         return out;
     }
     check_bf16(x, "x");
-    TORCH_CHECK(x.dim() == 4, "x must be NHWC");
+    check_pool(x, kernel, stride, pad, "avgpool2d");
     int NB = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
     TORCH_CHECK(C % 8 == 0, "C must be a multiple of 8");
     int OH = (int)((H + 2 * pad - kernel) / stride + 1);
@@ -1135,6 +1156,7 @@ Tensor global_avg_pool(Tensor x) {
     TORCH_CHECK(x.dim() == 4, "x must be NHWC");
     int NB = x.size(0), HW = x.size(1) * x.size(2), C = x.size(3);
     TORCH_CHECK(C % 8 == 0, "C must be a multiple of 8");
+    TORCH_CHECK(HW > 0, "empty spatial extent");
     auto out = at::empty({NB, C}, x.options());
     defer_hip::launch_gap(bptr(x), bptr_mut(out), NB, HW, C, cur_stream());
     return out;

@@ -82,7 +82,7 @@ __global__ void softmax_kernel(const bf16* __restrict__ x,
     int lane = threadIdx.x % WAVE;
     if (row >= rows) return;
     const bf16* xr = x + (long)row * cols;
-    float m = -1e30f;
+    float m = -INFINITY;
     for (int c = lane; c < cols; c += WAVE) m = fmaxf(m, bf2f(xr[c]));
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1)

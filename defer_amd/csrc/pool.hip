@@ -26,7 +26,7 @@ __global__ void maxpool_kernel(const bf16* __restrict__ x,
         int n = (int)(q / OH);
         float best[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) best[j] = -1e30f;
+        for (int j = 0; j < 8; ++j) best[j] = -INFINITY;
         int ih0 = oh * stride - pad, iw0 = ow * stride - pad;
         for (int r = 0; r < kh; ++r) {
             int ih = ih0 + r;

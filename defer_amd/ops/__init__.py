@@ -334,10 +334,37 @@ def stem_pool_stats():
     return _stats("stem_pool_stats")
 
 
+# The CPU branch of an op raises what the bindings raise for the same call,
+# so a model that runs on the CPU cannot fail on these later on the GPU.
+
+def _check_pool(name, x, kernel, stride, padding):
+    if x.dim() != 4:
+        raise RuntimeError(f"{name}: x must be NHWC, got {x.dim()}-D")
+    if kernel < 1:
+        raise RuntimeError(f"{name}: kernel must be >= 1, got {kernel}")
+    if stride < 1:
+        raise RuntimeError(f"{name}: stride must be >= 1, got {stride}")
+    if not 0 <= padding <= kernel // 2:
+        raise RuntimeError(
+            f"{name}: pad must be in [0, kernel / 2], got pad {padding} "
+            f"for kernel {kernel}")
+    h, w = x.shape[1], x.shape[2]
+    if h + 2 * padding < kernel or w + 2 * padding < kernel:
+        raise RuntimeError(
+            f"{name}: input {h}x{w} with pad {padding} is smaller than the "
+            f"window {kernel}")
+
+
 def batchnorm_apply(x, scale, bias, act="none"):
     _act_code(act, _RELU_OR_NONE)
     m = _backend(x)
     if m is None:
+        c = x.shape[-1] if x.dim() else 0
+        if (scale.device != x.device or bias.device != x.device
+                or scale.numel() != c or bias.numel() != c):
+            raise RuntimeError(
+                "batchnorm_apply: scale/bias must be tensors of length C "
+                "on x's device")
         return _ref.batchnorm_apply(x, scale, bias, act)
     return m.bn_act(x, scale, bias, act == "relu")
 
@@ -366,8 +393,13 @@ def relu6(x):
 
 
 def maxpool2d(x, kernel=3, stride=2, padding=1):
+    """Max over the window's in-bounds taps, NHWC (a window of -inf gives
+    -inf). Raises for kernel < 1, stride < 1, padding outside
+    [0, kernel // 2] and an input smaller than the window, like
+    F.max_pool2d; avgpool2d likewise."""
     m = _backend(x)
     if m is None:
+        _check_pool("maxpool2d", x, kernel, stride, padding)
         return _ref.maxpool2d(x, kernel, stride, padding)
     return m.maxpool2d(x, kernel, stride, padding)
 
@@ -375,6 +407,7 @@ def maxpool2d(x, kernel=3, stride=2, padding=1):
 def avgpool2d(x, kernel=2, stride=2, padding=0):
     m = _backend(x)
     if m is None:
+        _check_pool("avgpool2d", x, kernel, stride, padding)
         return _ref.avgpool2d(x, kernel, stride, padding)
     return m.avgpool2d(x, kernel, stride, padding)
 
@@ -392,6 +425,11 @@ def concat_channels(xs):
 def global_avg_pool(x):
     m = _backend(x)
     if m is None:
+        if x.dim() != 4:
+            raise RuntimeError(
+                f"global_avg_pool: x must be NHWC, got {x.dim()}-D")
+        if x.shape[1] * x.shape[2] == 0:
+            raise RuntimeError("global_avg_pool: empty spatial extent")
         return _ref.global_avg_pool(x)
     return m.global_avg_pool(x)
 
@@ -446,5 +484,7 @@ def linear(x, w, bias=None):
 def softmax(x):
     m = _backend(x)
     if m is None:
+        if x.dim() < 1 or x.numel() == 0:
+            raise RuntimeError("softmax of nothing")
         return _ref.softmax(x)
     return m.softmax(x)

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import defer_amd.ops as ops
+import ops_checks as checks
 from defer_amd.ops import reference as ref
 
 pytestmark = pytest.mark.gpu
@@ -167,6 +168,7 @@ def test_global_avg_pool():
     want = ref.global_avg_pool(xg.cpu())
     got = ops.global_avg_pool(xg)
     assert _relerr(got, want) < 0.01
+    checks.check_global_avg_pool(xg, got)
 
 
 @requires_gpu
@@ -222,6 +224,7 @@ def test_softmax():
     got = ops.softmax(xg)
     assert (got.float().cpu() - want.float()).abs().max() < 2e-3
     assert ((got.float().sum(-1) - 1).abs() < 2e-2).all()
+    checks.check_softmax(xg, got)
 
 
 @requires_gpu
@@ -229,13 +232,17 @@ def test_add_act_bn_act_relu():
     a = torch.randn(2, 14, 14, 1024)
     b = torch.randn(2, 14, 14, 1024)
     ag, bg = _to_dev_bf16(a, b)
-    assert _relerr(ops.add_act(ag, bg, "relu"),
-                   ref.add_act(ag.cpu(), bg.cpu(), "relu")) < 0.01
+    got = ops.add_act(ag, bg, "relu")
+    assert _relerr(got, ref.add_act(ag.cpu(), bg.cpu(), "relu")) < 0.01
+    checks.check_add_act(ag, bg, "relu", got)
     sc = torch.rand(1024) + 0.5
     bi = torch.randn(1024)
-    assert _relerr(ops.batchnorm_apply(ag, sc.to(DEV), bi.to(DEV), "relu"),
-                   ref.batchnorm_apply(ag.cpu(), sc, bi, "relu")) < 0.01
-    assert torch.equal(ops.relu(ag).cpu(), ref.relu(ag.cpu()))
+    got = ops.batchnorm_apply(ag, sc.to(DEV), bi.to(DEV), "relu")
+    assert _relerr(got, ref.batchnorm_apply(ag.cpu(), sc, bi, "relu")) < 0.01
+    checks.check_batchnorm_apply(ag, sc, bi, "relu", got)
+    got = ops.relu(ag)
+    assert torch.equal(got.cpu(), ref.relu(ag.cpu()))
+    checks.check_relu(ag, got)
 
 
 @requires_gpu
@@ -392,6 +399,7 @@ def test_avgpool_gpu():
         got = ops.avgpool2d(xg, k, s, p)
         assert got.shape == want.shape
         assert _relerr(got, want) < 0.005
+        checks.check_avgpool2d(xg, k, s, p, got)
 
 
 @requires_gpu
