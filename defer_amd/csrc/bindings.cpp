@@ -71,13 +71,14 @@ void check_pool(const Tensor& x, int64_t kernel, int64_t stride,
                 " is smaller than the window ", kernel);
 }
 
-// activation codes of the ops that know ReLU6 (ACT_* of csrc/common.h);
-// C++ callers that pass a bool get none / relu
-enum { kActNone = 0, kActRelu = 1, kActRelu6 = 2 };
+// activation codes of the ops that know ReLU6 and hardswish (ACT_* of
+// csrc/common.h); C++ callers that pass a bool get none / relu
+enum { kActNone = 0, kActRelu = 1, kActRelu6 = 2, kActHardswish = 3 };
 
 void check_act(int64_t act) {
-    TORCH_CHECK(act >= kActNone && act <= kActRelu6,
-                "act must be 0 (none), 1 (relu) or 2 (relu6), got ", act);
+    TORCH_CHECK(act >= kActNone && act <= kActHardswish,
+                "act must be 0 (none), 1 (relu), 2 (relu6) or 3 (hardswish), "
+                "got ", act);
 }
 
 // 16B zero source for OOB global_load_lds lanes, one per process
@@ -449,9 +450,12 @@ py::dict conv_plan(std::vector<int64_t> xs, std::vector<int64_t> ws,
 // launch_conv_igemm paths for the 3x3/s1/p1 64->64 bf16 class: 0 = the
 // measured policy, 1 = the new kernel wherever it covers the shape, 2 =
 // never. Shapes it does not cover run launch_conv_igemm under every mode.
-// max_blocks caps that kernel's grid (0 = policy). act: kActNone, kActRelu
-// or kActRelu6; ReLU6 runs the ReLU instantiation of whichever kernel the
-// plan names, with the upper bound 6 in ConvParams::act_hi.
+// max_blocks caps that kernel's grid (0 = policy). act: kActNone, kActRelu,
+// kActRelu6 or kActHardswish. ReLU6 runs the ReLU instantiation of whichever
+// kernel the plan names, with the upper bound 6 in ConvParams::act_hi;
+// hardswish has instantiations of its own (the third row of the launchers'
+// kernel tables). Every dtype applies the activation in fp32 before the one
+// rounding.
 Tensor conv2d_bn_act(Tensor x, Tensor w, c10::optional<Tensor> scale,
                      c10::optional<Tensor> bias, c10::optional<Tensor> res,
                      int64_t stride, int64_t pad, int64_t act,
@@ -462,7 +466,8 @@ Tensor conv2d_bn_act(Tensor x, Tensor w, c10::optional<Tensor> scale,
     if (is_f32(x, "x"))
         return conv2d_bn_act_f32(x, w, scale, bias, res, stride, pad,
                                  (int)act);
-    const bool relu = act != kActNone;
+    // the launchers' instantiation: 0 none, 1 relu (and relu6), 2 hardswish
+    const int kact = act == kActNone ? 0 : act == kActHardswish ? 2 : 1;
     check_bf16(x, "x");
     check_bf16(w, "w");
     TORCH_CHECK(x.dim() == 4, "x must be NHWC");
@@ -522,7 +527,7 @@ Tensor conv2d_bn_act(Tensor x, Tensor w, c10::optional<Tensor> scale,
     p.w = bptr(wp);
     const auto plan = plan_prepared(g, mode, max_blocks, variant);
     if (plan.family == defer_hip::ConvPlan::WS) {
-        auto used = defer_hip::launch_conv_ws(p, relu, (bool)res,
+        auto used = defer_hip::launch_conv_ws(p, kact, (bool)res,
                                               (int)max_blocks, s);
         auto& st = conv_ws_stats_ref();
         std::lock_guard<std::mutex> g2(st.mu);
@@ -531,7 +536,7 @@ Tensor conv2d_bn_act(Tensor x, Tensor w, c10::optional<Tensor> scale,
         st.tiles_per_block = used.tiles_per_block;
         return out;
     }
-    defer_hip::launch_conv_igemm(p, plan, relu, (bool)res, s);
+    defer_hip::launch_conv_igemm(p, plan, kact, (bool)res, s);
     return out;
 }
 
@@ -840,6 +845,118 @@ Tensor relu6(Tensor x) {
     defer_hip::launch_relu6(bptr(x), bptr_mut(out), x.numel() / 8,
                             cur_stream());
     return out;
+}
+
+Tensor hardswish(Tensor x) {
+    if (is_f32(x, "x")) {
+        check_f32(x, "x");
+        TORCH_CHECK(x.numel() % 4 == 0,
+                    "fp32 hardswish needs numel % 4 == 0");
+        auto out = at::empty_like(x);
+        defer_hip::launch_hardswish_f32(f32ptr(x), out.data_ptr<float>(),
+                                        x.numel() / 4, cur_stream());
+        return out;
+    }
+    check_bf16(x, "x");
+    TORCH_CHECK(x.numel() % 8 == 0, "numel must be a multiple of 8");
+    auto out = at::empty_like(x);
+    defer_hip::launch_hardswish(bptr(x), bptr_mut(out), x.numel() / 8,
+                                cur_stream());
+    return out;
+}
+
+// fp32 bias of one FC of squeeze_excite: absent = null (the kernel adds
+// nothing); present = fp32[n] on x's device, whatever the compute dtype
+const float* se_bias(const c10::optional<Tensor>& t, const char* name,
+                     int64_t n, const Tensor& x) {
+    if (!t) return nullptr;
+    TORCH_CHECK(t->device() == x.device() &&
+                t->scalar_type() == at::kFloat && t->is_contiguous() &&
+                t->dim() == 1 && t->numel() == n,
+                "squeeze_excite: ", name, " must be a contiguous fp32[", n,
+                "] on x's device");
+    return t->data_ptr<float>();
+}
+
+// The gate of squeeze-excite (csrc/se.hip), fp32 [N, C]:
+// g = hardsigmoid(w2 @ act(w1 @ mean_hw(x) + b1) + b2), all in fp32. One
+// launch on the current stream, no host sync. act: kActNone or kActRelu.
+// The kernel's LDS holds the C means and the Cr hidden values in fp32.
+Tensor se_gate(Tensor x, Tensor w1, c10::optional<Tensor> b1, Tensor w2,
+               c10::optional<Tensor> b2, int64_t act) {
+    TORCH_CHECK(act == kActNone || act == kActRelu,
+                "squeeze_excite: act must be 0 (none) or 1 (relu), got ",
+                act);
+    const bool f32 = is_f32(x, "x");
+    for (const Tensor* t : {&x, &w1, &w2}) {
+        const char* name = t == &x ? "x" : t == &w1 ? "w1" : "w2";
+        if (f32) check_f32(*t, name);
+        else check_bf16(*t, name);
+        TORCH_CHECK((uintptr_t)t->data_ptr() % 16 == 0, name,
+                    " must be 16-byte aligned");
+    }
+    TORCH_CHECK(w1.device() == x.device() && w2.device() == x.device(),
+                "squeeze_excite: w1 and w2 must be on x's device");
+    TORCH_CHECK(x.dim() == 4, "squeeze_excite: x must be NHWC, got ",
+                x.dim(), "-D");
+    int64_t NB = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+    const int vec = f32 ? 4 : 8;
+    TORCH_CHECK(C > 0 && C % vec == 0, "squeeze_excite: ",
+                f32 ? "fp32" : "bf16", " needs C % ", vec, " == 0, got ", C);
+    TORCH_CHECK(w1.dim() == 2 && w1.size(1) == C && w1.size(0) >= 1,
+                "squeeze_excite: w1 must be [Cr, C] with C = ", C);
+    const int64_t Cr = w1.size(0);
+    TORCH_CHECK(w2.dim() == 2 && w2.size(0) == C && w2.size(1) == Cr,
+                "squeeze_excite: w2 must be [C, Cr] = [", C, ", ", Cr, "]");
+    const float* bp1 = se_bias(b1, "b1", Cr, x);
+    const float* bp2 = se_bias(b2, "b2", C, x);
+    TORCH_CHECK(H * W > 0, "squeeze_excite: empty spatial extent");
+    TORCH_CHECK(H * W < (1LL << 30) && NB < (1LL << 31),
+                "squeeze_excite: H * W of 2^30 or a batch of 2^31 or more");
+    TORCH_CHECK(C + Cr <= defer_hip::SE_MAX_LDS_FLOATS,
+                "squeeze_excite: C + Cr must be at most ",
+                defer_hip::SE_MAX_LDS_FLOATS, ", got ", C + Cr);
+    auto g = at::empty({NB, C}, x.options().dtype(at::kFloat));
+    if (NB == 0) return g;
+    defer_hip::launch_se_gate(x.data_ptr(), w1.data_ptr(), bp1,
+                              w2.data_ptr(), bp2, g.data_ptr<float>(),
+                              (int)NB, (int)(H * W), (int)C, (int)Cr,
+                              (int)act, f32, cur_stream());
+    return g;
+}
+
+// y[n, h, w, c] = round(x[n, h, w, c] * g[n, c]): the scale pass of
+// squeeze-excite. x NHWC bf16 or fp32, g fp32 [N, C].
+Tensor channel_scale(Tensor x, Tensor g) {
+    const bool f32 = is_f32(x, "x");
+    if (f32) check_f32(x, "x");
+    else check_bf16(x, "x");
+    check_f32(g, "g");
+    TORCH_CHECK(g.device() == x.device(),
+                "channel_scale: g must be on x's device");
+    TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0,
+                "x must be 16-byte aligned");
+    TORCH_CHECK(x.dim() == 4, "channel_scale: x must be NHWC");
+    int64_t NB = x.size(0), HW = x.size(1) * x.size(2), C = x.size(3);
+    const int vec = f32 ? 4 : 8;
+    TORCH_CHECK(C > 0 && C % vec == 0, "channel_scale: ",
+                f32 ? "fp32" : "bf16", " needs C % ", vec, " == 0, got ", C);
+    TORCH_CHECK(g.dim() == 2 && g.size(0) == NB && g.size(1) == C,
+                "channel_scale: g must be [N, C] = [", NB, ", ", C, "]");
+    auto y = at::empty_like(x);
+    if (y.numel() == 0) return y;
+    defer_hip::launch_channel_scale(x.data_ptr(), g.data_ptr<float>(),
+                                    y.data_ptr(), NB, HW, (int)C, f32,
+                                    cur_stream());
+    return y;
+}
+
+// Squeeze-excite: y = x * se_gate(x, ...). Two launches, both
+// deterministic; g comes from torch's allocator, so the pair can be
+// captured into a hipGraph.
+Tensor squeeze_excite(Tensor x, Tensor w1, c10::optional<Tensor> b1,
+                      Tensor w2, c10::optional<Tensor> b2, int64_t act) {
+    return channel_scale(x, se_gate(x, w1, b1, w2, b2, act));
 }
 
 // fp32[C] scale / bias of the depthwise conv; absent = the cached ones /
@@ -1438,6 +1555,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("add_act", &add_act);
     m.def("relu", &relu);
     m.def("relu6", &relu6);
+    m.def("hardswish", &hardswish);
+    m.def("squeeze_excite", &squeeze_excite, py::arg("x"), py::arg("w1"),
+          py::arg("b1"), py::arg("w2"), py::arg("b2"), py::arg("act"));
+    m.def("se_gate", &se_gate, py::arg("x"), py::arg("w1"), py::arg("b1"),
+          py::arg("w2"), py::arg("b2"), py::arg("act"));
+    m.def("channel_scale", &channel_scale);
     m.def("softmax", &softmax);
     m.def("maxpool2d", &maxpool2d);
     m.def("avgpool2d", &avgpool2d);

@@ -39,8 +39,20 @@ __device__ __forceinline__ int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // activation codes
 // (ACT_RELU6 is a runtime value of the depthwise and fp32 conv kernels and
-// of the bindings; the bf16 conv templates take ACT_RELU with a bound)
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_RELU6 = 2 };
+// of the bindings; the bf16 conv templates take ACT_RELU with a bound for
+// it, and ACT_NONE, ACT_RELU or ACT_HARDSWISH as their ACT)
+enum { ACT_NONE = 0, ACT_RELU = 1, ACT_RELU6 = 2, ACT_HARDSWISH = 3 };
+
+// hardsigmoid(v) = min(max(v + 3, 0), 6) * (1/6), hardswish(v) = v * that,
+// in this order everywhere (ops/reference.py too): 6 * c6 and 3 * c6 round
+// to exactly 1 and 0.5, so hardswish returns v bit for bit for v >= 3 and 0
+// for v <= -3. No division and no fma: there is no product feeding a sum.
+__device__ __forceinline__ float hardsigmoid_f(float v) {
+    return fminf(fmaxf(v + 3.0f, 0.0f), 6.0f) * (1.0f / 6.0f);
+}
+__device__ __forceinline__ float hardswish_f(float v) {
+    return v * hardsigmoid_f(v);
+}
 
 __device__ __forceinline__ float apply_act(float v, int act) {
     return act == ACT_RELU ? fmaxf(v, 0.0f) : v;
@@ -48,7 +60,12 @@ __device__ __forceinline__ float apply_act(float v, int act) {
 
 // The bf16 conv epilogues: ACT_RELU clamps to [0, hi]. hi = +inf is the
 // plain ReLU (min(v, +inf) == v, so the bits are those of apply_act) and
-// hi = 6 is ReLU6, without a third template value per kernel.
+// hi = 6 is ReLU6, without a third template value per kernel. ACT_HARDSWISH
+// is a template value of its own: as a runtime flag inside the ReLU
+// instantiations it cost ResNet50 2.5 % (docs/OPTIMIZATION_LOG.md). act is a
+// compile-time constant at every call, so the ReLU and no-activation
+// instantiations are what they were.
 __device__ __forceinline__ float apply_act_hi(float v, int act, float hi) {
+    if (act == ACT_HARDSWISH) return hardswish_f(v);
     return act == ACT_RELU ? fminf(fmaxf(v, 0.0f), hi) : v;
 }

@@ -1260,12 +1260,14 @@ struct ConvRow {
     ConvPlan::Family family;
     const char* args;
     std::array<int, 7> key;
-    ConvKernel kernel[2][2];   // [relu][has_res]
+    ConvKernel kernel[3][2];   // [none, relu, hardswish][has_res]
 };
 #define ROW(F, K, ...)                                                    \
     {ConvPlan::F, #__VA_ARGS__, {{__VA_ARGS__}},                          \
      {{K<ACT_NONE, false, __VA_ARGS__>, K<ACT_NONE, true, __VA_ARGS__>},  \
-      {K<ACT_RELU, false, __VA_ARGS__>, K<ACT_RELU, true, __VA_ARGS__>}}}
+      {K<ACT_RELU, false, __VA_ARGS__>, K<ACT_RELU, true, __VA_ARGS__>},  \
+      {K<ACT_HARDSWISH, false, __VA_ARGS__>,                              \
+       K<ACT_HARDSWISH, true, __VA_ARGS__>}}}
 // a tile config without B_PERSIST serves all four gathers; with it (K
 // fits one tile) only GEMM and CONV
 #define IGEMM_ROWS(...)                                                   \
@@ -1315,8 +1317,10 @@ std::vector<std::string> conv_table_rows() {
     return rows;
 }
 
-void launch_conv_igemm(const ConvParams& p0, const ConvPlan& pl, bool relu,
+void launch_conv_igemm(const ConvParams& p0, const ConvPlan& pl, int act,
                        bool has_res, hipStream_t s) {
+    if (act < 0 || act > 2)
+        throw std::runtime_error("launch_conv_igemm: act must be 0, 1 or 2");
     static_assert(CONV_BK == BK && WIN_TW == WTW, "conv_plan.h tile sizes");
     ConvParams p = p0;
     if (pl.family != ConvPlan::SWIN) {
@@ -1327,7 +1331,7 @@ void launch_conv_igemm(const ConvParams& p0, const ConvPlan& pl, bool relu,
     }
     if (pl.family != ConvPlan::IGEMM)
         p.smul = pl.full_sync ? 1u : 0u;   // full-sync debug flag
-    hipLaunchKernelGGL(find_row(pl).kernel[relu][has_res],
+    hipLaunchKernelGGL(find_row(pl).kernel[act][has_res],
                        dim3(pl.grid_x, pl.grid_y), dim3(NTHREADS), 0, s, p);
 }
 

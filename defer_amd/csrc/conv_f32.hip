@@ -226,7 +226,10 @@ __global__ __launch_bounds__(F32_TPB) void conv_f32_kernel(
         if (bias) v = v + *reinterpret_cast<const f32x4*>(bias + n);
         long o = (long)m * Cout + n;
         if (res) v = v + *reinterpret_cast<const f32x4*>(res + o);
-        if (p.relu) {
+        if (p.relu == ACT_HARDSWISH) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = hardswish_f(v[e]);
+        } else if (p.relu) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
         }

@@ -301,18 +301,20 @@ inline ConvPlan plan_conv(const ConvParams& p, bool gemm_mode,
 // Launchers: take a plan, look the kernel up, launch; a plan with no
 // table row throws. launch_conv_igemm serves IGEMM, WIN and SWIN (the small-Cin
 // window stem path: Cin pre-padded to 8, weights pre-repacked j-major
-// zero-padded) and fills the magic-multiply reciprocals.
-void launch_conv_igemm(const ConvParams& p, const ConvPlan& plan, bool relu,
+// zero-padded) and fills the magic-multiply reciprocals. act picks the
+// instantiation: 0 = none, 1 = the ReLU clamped to ConvParams::act_hi, 2 =
+// hardswish (a bool gives none / relu).
+void launch_conv_igemm(const ConvParams& p, const ConvPlan& plan, int act,
                        bool has_res, hipStream_t s);
 // weight-stationary window kernel (conv_ws.hip): 3x3/s1/p1 convs with
 // Cin = Cout = 64 keep the whole weight tensor in registers and stage only
 // input windows to LDS; bit-identical to launch_conv_igemm on the same
-// ConvParams (relu or none, with or without residual).
+// ConvParams (act as in launch_conv_igemm, with or without residual).
 struct ConvWsLaunch {
     int blocks;            // grid size
     int tiles_per_block;   // 8x16 output tiles the busiest block walks
 };
-ConvWsLaunch launch_conv_ws(const ConvParams& p, bool relu, bool has_res,
+ConvWsLaunch launch_conv_ws(const ConvParams& p, int act, bool has_res,
                             int max_blocks, hipStream_t s);
 
 // The dispatch table, for ops.conv_plan and the tests: the template

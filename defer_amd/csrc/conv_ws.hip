@@ -305,8 +305,10 @@ __global__ __launch_bounds__(WS_TPB, 2) void conv_ws_kernel(ConvParams p) {
 
 namespace defer_hip {
 
-ConvWsLaunch launch_conv_ws(const ConvParams& p, bool relu, bool has_res,
+ConvWsLaunch launch_conv_ws(const ConvParams& p, int act, bool has_res,
                             int max_blocks, hipStream_t s) {
+    if (act < 0 || act > 2)
+        throw std::runtime_error("launch_conv_ws: act must be 0, 1 or 2");
     static_assert(WS_TH == 8 && WS_TW == WIN_TW && WS_K == 9 * CONV_BK,
                   "conv_plan.h plans 8x16 tiles");
     // mode 1: the caller has chosen this kernel; the plan is its grid
@@ -314,10 +316,12 @@ ConvWsLaunch launch_conv_ws(const ConvParams& p, bool relu, bool has_res,
     if (pl.family != ConvPlan::WS)
         throw std::runtime_error("no kernel for this plan: " +
                                  to_string(pl));
-    static void (*const kernel[2][2])(ConvParams) = {
+    static void (*const kernel[3][2])(ConvParams) = {
         {conv_ws_kernel<ACT_NONE, false>, conv_ws_kernel<ACT_NONE, true>},
-        {conv_ws_kernel<ACT_RELU, false>, conv_ws_kernel<ACT_RELU, true>}};
-    hipLaunchKernelGGL(kernel[relu][has_res], dim3(pl.blocks),
+        {conv_ws_kernel<ACT_RELU, false>, conv_ws_kernel<ACT_RELU, true>},
+        {conv_ws_kernel<ACT_HARDSWISH, false>,
+         conv_ws_kernel<ACT_HARDSWISH, true>}};
+    hipLaunchKernelGGL(kernel[act][has_res], dim3(pl.blocks),
                        dim3(WS_TPB), 0, s, p);
     return ConvWsLaunch{pl.blocks, pl.tiles_per_block};
 }

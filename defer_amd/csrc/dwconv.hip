@@ -189,8 +189,12 @@ __global__ __launch_bounds__(DW_TPB) void dwconv_kernel(
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 float v = fmaf(acc[o][j], sc[j], bi[j]);
-                if (act != ACT_NONE) v = fmaxf(v, 0.0f);
-                if (act == ACT_RELU6) v = fminf(v, 6.0f);
+                if (act == ACT_HARDSWISH) {
+                    v = hardswish_f(v);
+                } else {
+                    if (act != ACT_NONE) v = fmaxf(v, 0.0f);
+                    if (act == ACT_RELU6) v = fminf(v, 6.0f);
+                }
                 E::set(out, j, v);
             }
             *reinterpret_cast<Vec*>(

@@ -75,6 +75,19 @@ __global__ void relu6_kernel(const bf16* __restrict__ x,
     }
 }
 
+__global__ void hardswish_kernel(const bf16* __restrict__ x,
+                                 bf16* __restrict__ y, long total8) {
+    long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    long stride = (long)gridDim.x * blockDim.x;
+    for (long i = i0; i < total8; i += stride) {
+        bf16x8 v = load_bf16x8(x + i * 8);
+        bf16x8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = f2bf(hardswish_f(bf2f(v[j])));
+        store_bf16x8(y + i * 8, o);
+    }
+}
+
 // Row softmax: one wave per row, fp32 accumulation, arbitrary ncols.
 __global__ void softmax_kernel(const bf16* __restrict__ x,
                                bf16* __restrict__ y, int rows, int cols) {
@@ -151,6 +164,11 @@ void launch_relu(const void* x, void* y, long total8, hipStream_t s) {
 void launch_relu6(const void* x, void* y, long total8, hipStream_t s) {
     hipLaunchKernelGGL(relu6_kernel, dim3(grid1d(total8, 256)), dim3(256), 0,
                        s, (const bf16*)x, (bf16*)y, total8);
+}
+
+void launch_hardswish(const void* x, void* y, long total8, hipStream_t s) {
+    hipLaunchKernelGGL(hardswish_kernel, dim3(grid1d(total8, 256)),
+                       dim3(256), 0, s, (const bf16*)x, (bf16*)y, total8);
 }
 
 void launch_cat2(const void* a, const void* b, void* y, long rows,

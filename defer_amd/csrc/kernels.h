@@ -112,6 +112,7 @@ void launch_add_act(const void* a, const void* b, void* y, long total8,
                     bool relu, hipStream_t s);
 void launch_relu(const void* x, void* y, long total8, hipStream_t s);
 void launch_relu6(const void* x, void* y, long total8, hipStream_t s);
+void launch_hardswish(const void* x, void* y, long total8, hipStream_t s);
 // two-input NHWC channel concat (c1, c2 % 8 == 0)
 void launch_cat2(const void* a, const void* b, void* y, long rows,
                  int c1, int c2, hipStream_t s);
@@ -141,7 +142,7 @@ struct ConvF32Params {
     int M, K, Cout;
     int H, W, Cin;
     int OH, OW, S, stride, pad;
-    int relu;           // ACT_NONE, ACT_RELU or ACT_RELU6 of common.h
+    int relu;           // an ACT_* of common.h, ACT_HARDSWISH included
 };
 // tile: 0 = heuristic, 1 = 128x128, 2 = 128x64 (A/B measurement switch)
 void launch_conv_f32(const ConvF32Params& p, bool gemm_mode, int tile,
@@ -158,6 +159,8 @@ void launch_add_act_f32(const float* a, const float* b, float* y,
                         long total4, bool relu, hipStream_t s);
 void launch_relu_f32(const float* x, float* y, long total4, hipStream_t s);
 void launch_relu6_f32(const float* x, float* y, long total4, hipStream_t s);
+void launch_hardswish_f32(const float* x, float* y, long total4,
+                          hipStream_t s);
 void launch_cat2_f32(const float* a, const float* b, float* y, long rows,
                      int c1, int c2, hipStream_t s);
 void launch_softmax_f32(const float* x, float* y, int rows, int cols,
@@ -174,7 +177,7 @@ void launch_gap_f32(const float* x, float* y, int NB, int HW, int C,
 // depthwise conv + folded BN + activation (dwconv.hip), NHWC x and [R][S][C]
 // w with R == S in {3, 5}, stride in {1, 2}, 0 <= pad <= R / 2; C % 8 == 0
 // (bf16) or C % 4 == 0 (fp32); scale and bias non-null fp32[C]; act is
-// ACT_NONE, ACT_RELU or ACT_RELU6. Element offsets are 64-bit.
+// ACT_NONE, ACT_RELU, ACT_RELU6 or ACT_HARDSWISH. Element offsets are 64-bit.
 void launch_dwconv(const void* x, const void* w, const float* scale,
                    const float* bias, void* y, int NB, int H, int W, int C,
                    int OH, int OW, int R, int stride, int pad, int act,
@@ -183,6 +186,20 @@ void launch_dwconv_f32(const float* x, const float* w, const float* scale,
                        const float* bias, float* y, int NB, int H, int W,
                        int C, int OH, int OW, int R, int stride, int pad,
                        int act, hipStream_t s);
+
+// squeeze-excite (se.hip). launch_se_gate: g[n][c] = hardsigmoid(w2 @
+// act(w1 @ mean_hw(x[n]) + b1) + b2), fp32 [NB][C]; x is [NB][HW][C], w1
+// [Cr][C] and w2 [C][Cr] in the compute dtype (f32 ? float : bf16), b1 and
+// b2 fp32 or null; C % 8 == 0 (bf16) or C % 4 == 0 (fp32), Cr >= 1, HW >= 1,
+// C + Cr <= SE_MAX_LDS_FLOATS; act is ACT_NONE or ACT_RELU.
+// launch_channel_scale: y = x * g[n][c], 64-bit element offsets.
+constexpr int SE_MAX_LDS_FLOATS = 8192;
+void launch_se_gate(const void* x, const void* w1, const float* b1,
+                    const void* w2, const float* b2, float* g, int NB,
+                    int HW, int C, int Cr, int act, bool f32,
+                    hipStream_t s);
+void launch_channel_scale(const void* x, const float* g, void* y, long NB,
+                          long HW, int C, bool f32, hipStream_t s);
 
 // NCHW <-> NHWC conversion with an optional fp32 <-> bf16 conversion in the
 // same pass (layout.hip). x is [N, C, HW] when to_nhwc, [N, HW, C]

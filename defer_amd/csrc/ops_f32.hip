@@ -72,6 +72,18 @@ __global__ void relu6_f32_kernel(const float* __restrict__ x,
     }
 }
 
+__global__ void hardswish_f32_kernel(const float* __restrict__ x,
+                                     float* __restrict__ y, long total4) {
+    long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    long stride = (long)gridDim.x * blockDim.x;
+    for (long i = i0; i < total4; i += stride) {
+        f32x4 v = ld4(x + i * 4), o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = hardswish_f(v[j]);
+        st4(y + i * 4, o);
+    }
+}
+
 // Row softmax: one wave per row, arbitrary ncols, accurate expf.
 __global__ void softmax_f32_kernel(const float* __restrict__ x,
                                    float* __restrict__ y, int rows,
@@ -206,6 +218,12 @@ void launch_relu_f32(const float* x, float* y, long total4, hipStream_t s) {
 
 void launch_relu6_f32(const float* x, float* y, long total4, hipStream_t s) {
     hipLaunchKernelGGL(relu6_f32_kernel, dim3(grid1d(total4, 256)),
+                       dim3(256), 0, s, x, y, total4);
+}
+
+void launch_hardswish_f32(const float* x, float* y, long total4,
+                          hipStream_t s) {
+    hipLaunchKernelGGL(hardswish_f32_kernel, dim3(grid1d(total4, 256)),
                        dim3(256), 0, s, x, y, total4);
 }
 

@@ -17,15 +17,19 @@ and shared between consumers.
 
 The patterns:
 
-    Conv2d [+ BatchNorm2d] [+ ReLU | ReLU6]        -> ConvBNAct
-    depthwise Conv2d [+ BatchNorm2d] [+ ReLU | ReLU6]
+    Conv2d [+ BatchNorm2d] [+ ReLU | ReLU6 | Hardswish]
+                                                   -> ConvBNAct
+    depthwise Conv2d [+ BatchNorm2d] [+ ReLU | ReLU6 | Hardswish]
         (groups == in == out channels, 3x3 or 5x5, stride 1 or 2,
          padding <= k // 2, C % 8 == 0)            -> DepthwiseConvBNAct
+    v * hardsigmoid(conv1x1(relu(conv1x1(pool(v)))))
+        (squeeze-excite, see below)                -> SqueezeExcite
     BatchNorm2d [+ ReLU]                           -> BNAct
     a + b [+ ReLU]                                 -> AddAct
     Linear [+ ReLU]                                -> Dense
     ReLU anywhere else                             -> Relu
     ReLU6 anywhere else                            -> Relu6
+    Hardswish anywhere else                        -> Hardswish
     MaxPool2d / AvgPool2d                          -> MaxPool / AvgPool
     AdaptiveAvgPool2d(1) or F.adaptive_avg_pool2d(x, 1) + flatten,
         mean over dims (2, 3)                      -> GlobalAvgPool
@@ -33,7 +37,17 @@ The patterns:
 
 ReLU6 is `nn.ReLU6`, `F.relu6`, `nn.Hardtanh(0., 6.)` or
 `F.hardtanh(x, 0., 6.)`. Every other grouped conv (groups between 1 and C,
-a channel multiplier) stays an island.
+a channel multiplier) stays an island. Hardswish is `nn.Hardswish` or
+`F.hardswish`, in place or not.
+
+Squeeze-excite is a `mul` (`a * b`, `torch.mul`, `a.mul(b)`, either operand
+order) of a 4-D value v with the chain `AdaptiveAvgPool2d(1)` |
+`F.adaptive_avg_pool2d(v, 1)` | `v.mean((2, 3), keepdim=True)` -> 1x1
+Conv2d C -> Cr -> ReLU or nothing -> 1x1 Conv2d Cr -> C -> `nn.Hardsigmoid`
+| `F.hardsigmoid`, bias optional on both convs, in which every node has the
+next as its only consumer and C % 8 == 0. Any other such chain (a sigmoid
+gate, a SiLU between the convs, a value of the chain read elsewhere) stays
+islands, with the reason on its pooling node.
 
 A pattern (conv [+ BN] [+ ReLU], add [+ ReLU], linear [+ ReLU], ...) is
 fused only through intermediates with exactly one consumer, and the fused
@@ -43,7 +57,8 @@ HIP op accepts its shape in both compute dtypes (the `TORCH_CHECK`s of
 `csrc/bindings.cpp`); anything else stays an island, with the reason
 recorded in the `TorchIsland` that wraps it.
 
-In-place ops: torch writes an in-place ReLU, ReLU6 or `a += b` into its input,
+In-place ops: torch writes an in-place ReLU, ReLU6, Hardswish or `a += b`
+into its input,
 so a later reader of that tensor sees the result. The lowered ops are out
 of place; such a node, when its input has other readers, is emitted on
 its own and the input's name is rebound to its output for everything that
@@ -195,18 +210,26 @@ class _Lowering:
                 and self._arg(n, 1, "min_val", -1.0) == 0
                 and self._arg(n, 2, "max_val", 1.0) == 6)
 
+    def is_hardswish(self, n, of) -> bool:
+        """nn.Hardswish or F.hardswish, in place or not"""
+        if not n.args or n.args[0] is not of:
+            return False
+        if n.op == "call_module":
+            return type(self.mod(n)) is nn.Hardswish
+        return n.op == "call_function" and n.target is F.hardswish
+
     def mutates_input(self, n) -> bool:
-        """An in-place ReLU, ReLU6 or `a += b`: torch writes the result into
-        args[0], so every LATER reader of that tensor sees it."""
+        """An in-place ReLU, ReLU6, Hardswish or `a += b`: torch writes the
+        result into args[0], so every LATER reader of that tensor sees it."""
         if n.op == "call_module":
             m = self.mod(n)
-            return (type(m) in (nn.ReLU, nn.ReLU6, nn.Hardtanh)
+            return (type(m) in (nn.ReLU, nn.ReLU6, nn.Hardtanh, nn.Hardswish)
                     and m.inplace)
         if n.op == "call_function":
             if n.target in (torch.relu_, F.relu_, F.hardtanh_,
                             operator.iadd):
                 return True
-            if n.target in (F.relu, F.relu6):
+            if n.target in (F.relu, F.relu6, F.hardswish):
                 return bool(self._arg(n, 1, "inplace", False))
             return n.target is F.hardtanh and bool(
                 self._arg(n, 3, "inplace", False))
@@ -232,14 +255,16 @@ class _Lowering:
         return u if u is not None and self.is_relu(u, n) else None
 
     def act_after(self, n):
-        """(node, "relu" | "relu6") for the activation that is `n`'s only
-        consumer, for the convs, whose kernels apply either; (None, "none")
-        otherwise."""
+        """(node, "relu" | "relu6" | "hardswish") for the activation that is
+        `n`'s only consumer, for the convs, whose kernels apply any of them;
+        (None, "none") otherwise."""
         u = self.sole_user(n)
         if u is not None and self.is_relu(u, n):
             return u, "relu"
         if u is not None and self.is_relu6(u, n):
             return u, "relu6"
+        if u is not None and self.is_hardswish(u, n):
+            return u, "hardswish"
         return None, "none"
 
     def is_flatten1(self, n, of) -> bool:
@@ -410,19 +435,151 @@ class _Lowering:
         self.rebind_mutated(n)
         return None
 
-    def lower_relu6(self, n) -> Optional[str]:
+    def lower_relu6(self, n, what="ReLU6", op="relu6",
+                    layer=L.Relu6) -> Optional[str]:
+        """A ReLU6, or a Hardswish (same numel rule), on its own."""
         s = self.shape(n)
         if s is None:
-            return "ReLU6 of a value of unknown shape"
+            return f"{what} of a value of unknown shape"
         numel = 1
         for d in s:
             numel *= d
         if numel % _VEC:
-            return (f"ReLU6 of {numel} elements: relu6 needs "
+            return (f"{what} of {numel} elements: {op} needs "
                     f"numel % {_VEC} == 0")
         layout = NHWC if len(s) == 4 else None
-        self.emit(n, L.Relu6(), [self.use(n.args[0], layout)], layout, [n])
+        self.emit(n, layer(), [self.use(n.args[0], layout)], layout, [n])
         self.rebind_mutated(n)
+        return None
+
+    def lower_hardswish(self, n) -> Optional[str]:
+        return self.lower_relu6(n, "Hardswish", "hardswish", L.Hardswish)
+
+    # ------------------------------------------------------ squeeze-excite
+    def _what(self, n) -> str:
+        m = self.mod(n)
+        return type(m).__name__ if m is not None else getattr(
+            n.target, "__name__", str(n.target))
+
+    def is_pool_to_1x1(self, n) -> bool:
+        """AdaptiveAvgPool2d(1), F.adaptive_avg_pool2d(v, 1) or
+        v.mean((2, 3), keepdim=True) of a 4-D value v"""
+        import torch.fx as fx
+
+        if not n.args or not isinstance(n.args[0], fx.Node):
+            return False
+        s = self.shape(n.args[0])
+        if s is None or len(s) != 4:
+            return False
+        m = self.mod(n)
+        if type(m) is nn.AdaptiveAvgPool2d:
+            return _pair(m.output_size) == (1, 1)
+        if n.op == "call_function" and n.target is F.adaptive_avg_pool2d:
+            return _pair(self._arg(n, 1, "output_size", None)) == (1, 1)
+        if ((n.op == "call_function" and n.target is torch.mean)
+                or (n.op == "call_method" and n.target == "mean")):
+            dim = self._arg(n, 1, "dim", None)
+            return (isinstance(dim, (tuple, list))
+                    and sorted(d % 4 for d in dim) == [2, 3]
+                    and bool(self._arg(n, 2, "keepdim", False))
+                    and n.kwargs.get("dtype") is None)
+        return False
+
+    def is_fc_conv(self, n, of) -> bool:
+        """a 1x1 / stride 1 / no padding, ungrouped Conv2d of `of`"""
+        m = self.mod(n)
+        return (type(m) is nn.Conv2d and len(n.args) == 1
+                and n.args[0] is of and _pair(m.kernel_size) == (1, 1)
+                and _pair(m.stride) == (1, 1) and m.groups == 1
+                and not isinstance(m.padding, str)
+                and _pair(m.padding) == (0, 0)
+                and _pair(m.dilation) == (1, 1))
+
+    def is_mul_of(self, n, a, b) -> bool:
+        if not self.is_mul(n):
+            return False
+        return (len(n.args) == 2 and not n.kwargs
+                and (n.args == (a, b) or n.args == (b, a)))
+
+    def is_mul(self, n) -> bool:
+        return ((n.op == "call_function"
+                 and n.target in (operator.mul, torch.mul))
+                or (n.op == "call_method" and n.target == "mul"))
+
+    def feeds_mul_with(self, n, v, depth=6) -> bool:
+        """Some value made from `n` within `depth` nodes is multiplied with
+        `v`: what tells a squeeze-excite from any other pooled branch (an
+        image-pooling branch, a conv head after the global pool)."""
+        if depth == 0:
+            return False
+        return any((self.is_mul(u) and v in u.args)
+                   or self.feeds_mul_with(u, v, depth - 1) for u in n.users)
+
+    def lower_squeeze_excite(self, n):
+        """`n` pools a 4-D value v to 1x1. False when this is no
+        squeeze-excite, that is when no 1x1 conv reads the pool or nothing
+        made from it is multiplied with v (the caller goes on with the other
+        patterns); None when the chain was lowered, else why it was not."""
+        elsewhere = ("squeeze-excite: the output of {} is read by more than "
+                     "the next node of the chain")
+        v = n.args[0]
+        if (not any(self.is_fc_conv(u, n) for u in n.users)
+                or not self.feeds_mul_with(n, v)):
+            return False
+        c1 = self.sole_user(n)
+        if c1 is None or not self.is_fc_conv(c1, n):
+            return elsewhere.format(self._what(n))
+        chain = [n, c1]
+        u = self.sole_user(c1)
+        if u is None:
+            return elsewhere.format("the first conv")
+        act = "none"
+        if self.is_relu(u, c1):
+            act = "relu"
+            chain.append(u)
+            c2 = self.sole_user(u)
+            if c2 is None:
+                return elsewhere.format("the ReLU")
+        else:
+            c2 = u
+        if not self.is_fc_conv(c2, chain[-1]):
+            return (f"squeeze-excite with {self._what(c2)} after its first "
+                    "conv: squeeze_excite takes a ReLU or nothing there")
+        chain.append(c2)
+        gate = self.sole_user(c2)
+        if gate is None:
+            return elsewhere.format("the second conv")
+        if not (gate.args and gate.args[0] is c2
+                and (type(self.mod(gate)) is nn.Hardsigmoid
+                     or (gate.op == "call_function"
+                         and gate.target is F.hardsigmoid))):
+            return (f"squeeze-excite with the gate {self._what(gate)}: "
+                    "squeeze_excite has the hardsigmoid gate only")
+        chain.append(gate)
+        mul = self.sole_user(gate)
+        if mul is None:
+            return elsewhere.format("the gate")
+        if not self.is_mul_of(mul, gate, v):
+            return ("squeeze-excite whose gate is not multiplied with the "
+                    "pooled value")
+        chain.append(mul)
+        m1, m2 = self.mod(c1), self.mod(c2)
+        c, cr = m1.in_channels, m1.out_channels
+        if (m2.in_channels, m2.out_channels) != (cr, c):
+            return (f"squeeze-excite convs {c} -> {cr} and "
+                    f"{m2.in_channels} -> {m2.out_channels} do not pair up")
+        if c % _VEC:
+            return (f"squeeze-excite on C={c}: squeeze_excite needs "
+                    f"C % {_VEC} == 0")
+        layer = L.SqueezeExcite(c, cr, act=act, gate="hardsigmoid")
+        for w, b, m in (("w1", "b1", m1), ("w2", "b2", m2)):
+            setattr(layer, w, nn.Parameter(   # [Cout, Cin, 1, 1] -> 2-D
+                m.weight.detach().float().reshape(
+                    m.out_channels, m.in_channels).clone()))
+            if m.bias is not None:
+                setattr(layer, b, nn.Parameter(
+                    m.bias.detach().float().clone()))
+        self.emit(mul, layer, [self.use(v, NHWC)], NHWC, chain)
         return None
 
     def lower_pool(self, n) -> Optional[str]:
@@ -574,6 +731,10 @@ class _Lowering:
         """None when `n` (and what it fuses with) was lowered, else why
         it stays an island."""
         m = self.mod(n)
+        if self.is_pool_to_1x1(n):
+            why = self.lower_squeeze_excite(n)
+            if why is not False:
+                return why
         if m is not None:
             if type(m) is nn.Conv2d:
                 return self.lower_conv(n)
@@ -607,11 +768,11 @@ class _Lowering:
             return self.lower_relu(n)
         if n.args and self.is_relu6(n, n.args[0]):
             return self.lower_relu6(n)
+        if n.args and self.is_hardswish(n, n.args[0]):
+            return self.lower_hardswish(n)
         if n.args and self.is_flatten1(n, n.args[0]):
             return self.lower_flatten(n)
-        what = type(m).__name__ if m is not None else getattr(
-            n.target, "__name__", str(n.target))
-        return f"no lowering for {what}"
+        return f"no lowering for {self._what(n)}"
 
     def island(self, n, reason: str):
         layer, refs = fx_call_layer(n, self.modules)

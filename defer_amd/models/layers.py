@@ -4,7 +4,8 @@ Each layer is a thin nn.Module over `defer_amd.ops` (HIP kernels on GPU,
 fp32 PyTorch reference on CPU). These are the in-repo replacements for the
 Keras layer zoo the reference executes via model.predict (node.py:106):
 Conv2D/BatchNorm/ReLU -> ConvBNAct (BN folded at init), DepthwiseConv2D/
-BatchNorm/ReLU6 -> DepthwiseConvBNAct, Add(+ReLU) ->
+BatchNorm/ReLU6 -> DepthwiseConvBNAct, the squeeze-excite block of
+MobileNetV3 -> SqueezeExcite, Add(+ReLU) ->
 AddAct, MaxPooling2D -> MaxPool, GlobalAveragePooling2D -> GlobalAvgPool,
 Dense -> Dense, softmax -> Softmax.
 
@@ -23,7 +24,8 @@ from defer_amd import ops
 
 
 class ConvBNAct(nn.Module):
-    """Conv2d + folded inference BatchNorm + optional ReLU or ReLU6, fused.
+    """Conv2d + folded inference BatchNorm + optional ReLU, ReLU6 or
+    hardswish, fused.
 
     BN folding: y = conv(x) * scale + bias with scale = gamma/sqrt(var+eps),
     bias = beta - mean*scale. Random init keeps BN-ish statistics so
@@ -88,6 +90,41 @@ class DepthwiseConvBNAct(nn.Module):
 
     def flops_per_pixel(self):
         return 2 * self.kernel * self.kernel * self.c
+
+
+class SqueezeExcite(nn.Module):
+    """Squeeze-excite: x * gate(fc2(act(fc1(mean over H, W of x)))), one
+    graph node with one input (ops.squeeze_excite; csrc/se.hip on the GPU).
+    fc1 is c -> cr and fc2 cr -> c, the 1x1 convs of the torch and Keras
+    blocks. Both weights are 2-D, so StageExecutor casts them to the compute
+    dtype with the conv weights; the biases are 1-D and stay fp32."""
+
+    def __init__(self, c, cr, act="relu", gate="hardsigmoid"):
+        super().__init__()
+        ops._act_code(act, ops._RELU_OR_NONE)
+        if gate not in ops._SE_GATES:
+            raise ValueError(
+                f"gate={gate!r}: expected one of {list(ops._SE_GATES)}")
+        self.c, self.cr = c, cr
+        self.act, self.gate = act, gate
+        self.w1 = nn.Parameter(torch.randn(cr, c) * math.sqrt(2.0 / c))
+        self.b1 = nn.Parameter(torch.zeros(cr))
+        self.w2 = nn.Parameter(torch.randn(c, cr) * math.sqrt(1.0 / cr))
+        self.b2 = nn.Parameter(torch.zeros(c))
+
+    def forward(self, x):
+        return ops.squeeze_excite(
+            x, self.w1.to(x.dtype), self.b1, self.w2.to(x.dtype), self.b2,
+            act=self.act, gate=self.gate)
+
+    def extra_repr(self):
+        return (f"squeeze_excite={self.c}->{self.cr}->{self.c} "
+                f"act={self.act} gate={self.gate}")
+
+    def flops_per_image(self):
+        """The two FCs; the pool and the scale are passes over the tensor,
+        which the partitioner costs by their bytes."""
+        return 4 * self.c * self.cr
 
 
 class AddAct(nn.Module):
@@ -211,6 +248,7 @@ class Flatten(nn.Module):
 class Dense(nn.Module):
     def __init__(self, cin, cout, bias=True, act="none"):
         super().__init__()
+        ops._act_code(act, ops._RELU_OR_NONE)
         self.cin, self.cout = cin, cout
         self.act = act
         self.weight = nn.Parameter(
@@ -241,6 +279,13 @@ class Relu6(nn.Module):
 
     def forward(self, x):
         return ops.relu6(x)
+
+
+class Hardswish(nn.Module):
+    """A hardswish that no conv or depthwise conv could take in."""
+
+    def forward(self, x):
+        return ops.hardswish(x)
 
 
 class ToNHWC(nn.Module):

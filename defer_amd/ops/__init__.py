@@ -84,8 +84,9 @@ def _stats(name):
 
 
 # activation names -> the codes of the bindings (ACT_* of csrc/common.h)
-_ACT_CODES = {"none": 0, "relu": 1, "relu6": 2}
+_ACT_CODES = {"none": 0, "relu": 1, "relu6": 2, "hardswish": 3}
 _RELU_OR_NONE = ("relu", "none")
+_SE_GATES = ("hardsigmoid",)
 
 
 def _act_code(act, known=tuple(_ACT_CODES), what="act"):
@@ -113,9 +114,10 @@ def conv2d_bn_act(x, w, scale=None, bias=None, stride=1, padding=1,
     bit-identical to the general paths. mode: 0 = policy, 1 = that kernel
     wherever it covers the shape, 2 = never; None = DEFER_CONV_WS. Every
     other shape or dtype runs the general paths under every mode.
-    max_blocks caps that kernel's grid (0 = policy). act: "none", "relu" or
-    "relu6" (min(max(v, 0), 6)), applied after scale, bias and residual and
-    before the rounding to the output dtype."""
+    max_blocks caps that kernel's grid (0 = policy). act: "none", "relu",
+    "relu6" (min(max(v, 0), 6)) or "hardswish" (v * (min(max(v + 3, 0), 6)
+    * (1/6)), see hardswish), applied after scale, bias and residual and
+    before the one rounding to the output dtype."""
     code = _act_code(act)
     m = _backend(x)
     if m is None:
@@ -390,6 +392,93 @@ def relu6(x):
     if m is None:
         return _ref.relu6(x)
     return m.relu6(x)
+
+
+def hardswish(x):
+    """x * hardsigmoid(x) with hardsigmoid(v) = min(max(v + 3, 0), 6) * c6,
+    c6 = 1/6 in fp32, evaluated in fp32 in exactly this order with one
+    rounding to x's dtype: x for x >= 3 and 0 for x <= -3, bit for bit.
+    relu's numel rules on the GPU."""
+    m = _backend(x)
+    if m is None:
+        return _ref.hardswish(x)
+    return m.hardswish(x)
+
+
+def _check_squeeze_excite(x, w1, b1, w2, b2):
+    """What the binding refuses, for the CPU branch."""
+    if x.dim() != 4:
+        raise RuntimeError(
+            f"squeeze_excite: x must be NHWC, got {x.dim()}-D")
+    if w1.dtype != x.dtype or w2.dtype != x.dtype:
+        raise RuntimeError(
+            f"squeeze_excite: w1 and w2 must be {x.dtype} like x (mixed "
+            f"dtypes), got {w1.dtype} and {w2.dtype}")
+    if not (x.is_contiguous() and w1.is_contiguous()
+            and w2.is_contiguous()):
+        raise RuntimeError("squeeze_excite: x, w1 and w2 must be contiguous")
+    c = x.shape[3]
+    if w1.dim() != 2 or w1.shape[1] != c or w1.shape[0] < 1:
+        raise RuntimeError(
+            f"squeeze_excite: w1 must be [Cr, C] with C = {c}")
+    cr = w1.shape[0]
+    if w2.dim() != 2 or tuple(w2.shape) != (c, cr):
+        raise RuntimeError(
+            f"squeeze_excite: w2 must be [C, Cr] = [{c}, {cr}]")
+    for name, b, n in (("b1", b1, cr), ("b2", b2, c)):
+        if b is not None and (b.device != x.device
+                              or b.dtype != torch.float32
+                              or not b.is_contiguous()
+                              or tuple(b.shape) != (n,)):
+            raise RuntimeError(
+                f"squeeze_excite: {name} must be a contiguous fp32[{n}] on "
+                "x's device")
+    if x.shape[1] * x.shape[2] == 0:
+        raise RuntimeError("squeeze_excite: empty spatial extent")
+
+
+def squeeze_excite(x, w1, b1, w2, b2, act="relu", gate="hardsigmoid"):
+    """Squeeze-excite of an NHWC x with w1 [Cr, C] and w2 [C, Cr] in x's
+    dtype (bf16 or fp32) and fp32 biases b1 [Cr], b2 [C] (or None):
+
+        s = mean over H, W of x                  (fp32, [N, C])
+        z = act(w1 @ s + b1)                     (fp32, [N, Cr])
+        g = gate(w2 @ z + b2)                    (fp32, [N, C])
+        y = round_to_dtype(x * g)
+
+    act is "relu" or "none", gate is "hardsigmoid" (see hardswish). s, z and
+    g are never rounded to bf16. On the GPU two HIP launches (csrc/se.hip):
+    the gate, one workgroup per image, and the scale pass; no atomics, every
+    sum in a fixed order, run-to-run identical. C % 8 == 0 (bf16) or
+    C % 4 == 0 (fp32), any Cr >= 1; N == 0 gives an empty tensor."""
+    code = _act_code(act, _RELU_OR_NONE)
+    if gate not in _SE_GATES:
+        raise ValueError(
+            f"gate={gate!r}: expected one of {list(_SE_GATES)}")
+    m = _backend(x)
+    if m is None:
+        _check_squeeze_excite(x, w1, b1, w2, b2)
+        return _ref.squeeze_excite(x, w1, b1, w2, b2, act, gate)
+    return m.squeeze_excite(x, w1, b1, w2, b2, code)
+
+
+def se_gate(x, w1, b1, w2, b2, act="relu"):
+    """The fp32 [N, C] gate g of squeeze_excite, and channel_scale(x, g) its
+    second pass: the two launches apart, for tools/sebench.py. GPU only."""
+    code = _act_code(act, _RELU_OR_NONE)
+    return _gpu_only(x, "se_gate").se_gate(x, w1, b1, w2, b2, code)
+
+
+def channel_scale(x, g):
+    """round_to_dtype(x * g[n, c]) for NHWC x and fp32 g [N, C]. GPU only."""
+    return _gpu_only(x, "channel_scale").channel_scale(x, g)
+
+
+def _gpu_only(x, name):
+    m = _backend(x)
+    if m is None:
+        raise RuntimeError(f"{name}: GPU tensors only")
+    return m
 
 
 def maxpool2d(x, kernel=3, stride=2, padding=1):

@@ -17,14 +17,34 @@ import torch
 import torch.nn.functional as F
 
 
-def apply_act(y: torch.Tensor, act: str, known=("none", "relu", "relu6")):
-    """The activation `act` of `y`; a name outside `known` raises."""
+# 1/6 rounded to fp32, the constant of the kernels (csrc/common.h)
+_C6 = float(torch.tensor(1.0, dtype=torch.float32) / 6.0)
+
+
+def _hardsigmoid_f32(v: torch.Tensor) -> torch.Tensor:
+    """min(max(v + 3, 0), 6) * c6 of an fp32 tensor, in the kernels' order:
+    6 * c6 and 3 * c6 round to exactly 1 and 0.5."""
+    return torch.clamp(v + 3.0, 0.0, 6.0) * _C6
+
+
+def _hardswish_f32(v: torch.Tensor) -> torch.Tensor:
+    """v * hardsigmoid(v): v bit for bit for v >= 3, 0 for v <= -3. No
+    division and no fma, unlike torch's own x * relu6(x + 3) / 6."""
+    return v * _hardsigmoid_f32(v)
+
+
+def apply_act(y: torch.Tensor, act: str,
+              known=("none", "relu", "relu6", "hardswish")):
+    """The activation `act` of the fp32 tensor `y`; a name outside `known`
+    raises."""
     if act not in known:
         raise ValueError(f"act={act!r}: expected one of {list(known)}")
     if act == "relu":
         return torch.relu(y)
     if act == "relu6":
         return torch.clamp(y, 0.0, 6.0)
+    if act == "hardswish":
+        return _hardswish_f32(y)
     return y
 
 
@@ -38,7 +58,7 @@ def conv2d_bn_act(
     bias: Optional[torch.Tensor],   # [K] folded BN shift / conv bias
     stride: int = 1,
     padding: int = 0,
-    act: str = "none",          # "none" | "relu" | "relu6"
+    act: str = "none",          # "none" | "relu" | "relu6" | "hardswish"
     residual: Optional[torch.Tensor] = None,  # [N, OH, OW, K] added pre-act
 ) -> torch.Tensor:
     """Fused conv + (folded) batchnorm + residual-add + activation.
@@ -97,6 +117,36 @@ def relu(x):
 
 def relu6(x):
     return torch.clamp(x, 0.0, 6.0)
+
+
+def hardswish(x):
+    """x * (min(max(x + 3, 0), 6) * c6) in fp32, one rounding to x's dtype."""
+    return _hardswish_f32(x.float()).to(x.dtype)
+
+
+def squeeze_excite(x, w1, b1, w2, b2, act="relu", gate="hardsigmoid"):
+    """Squeeze-excite, x [N, H, W, C], w1 [Cr, C], w2 [C, Cr], biases [Cr]
+    and [C] or None:
+
+        s = mean over H, W of x          [N, C]
+        z = act(w1 @ s + b1)             [N, Cr]
+        g = gate(w2 @ z + b2)            [N, C]
+        y = x * g
+
+    s, z and g are fp32 and never rounded to x's dtype; y is rounded once."""
+    if gate != "hardsigmoid":
+        raise ValueError(f"gate={gate!r}: expected one of ['hardsigmoid']")
+    xf = x.float()
+    s = xf.mean(dim=(1, 2))
+    z = s @ w1.float().t()
+    if b1 is not None:
+        z = z + b1.float()
+    z = apply_act(z, act, _RELU_ONLY)
+    v = z @ w2.float().t()
+    if b2 is not None:
+        v = v + b2.float()
+    g = _hardsigmoid_f32(v)
+    return (xf * g[:, None, None, :]).to(x.dtype)
 
 
 def maxpool2d(x, kernel=3, stride=2, padding=1):

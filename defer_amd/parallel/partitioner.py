@@ -134,6 +134,12 @@ def node_times(graph: LayerGraph, input_shape=(1, 224, 224, 3),
             # kernels' rate
             f = float(out[0] * out[1] * out[2]) * lay.flops_per_pixel()
             t = (in_b + out_b) / _BW_ELTW
+        elif isinstance(lay, L.SqueezeExcite):
+            # three passes over the tensor at the streaming kernels' rate:
+            # the pool reads it, the scale pass reads it again and writes
+            # the output; the two FCs are noise beside them
+            f = float(out[0]) * lay.flops_per_image()
+            t = (2 * in_b + out_b) / _BW_ELTW
         elif isinstance(lay, nn.Conv2d):
             # FX-imported models carry plain torch convs (NCHW):
             # out = (B, C, H, W)

@@ -19,7 +19,7 @@ ROOT = Path(__file__).parent
 CSRC = ROOT / "defer_amd" / "csrc"
 
 sources = [str(CSRC / f) for f in
-           ["bindings.cpp", "conv.hip", "conv_ws.hip", "prebn.hip", "chain.hip", "stem_pool.hip", "elementwise.hip", "pool.hip", "dwconv.hip",
+           ["bindings.cpp", "conv.hip", "conv_ws.hip", "prebn.hip", "chain.hip", "stem_pool.hip", "elementwise.hip", "pool.hip", "dwconv.hip", "se.hip",
             "layout.hip", "codec.hip", "lz4.hip", "pack.hip", "conv_f32.hip", "ops_f32.hip"]
            if (CSRC / f).exists()]
 

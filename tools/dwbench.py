@@ -2,6 +2,7 @@
 MobileNetV2, on one GPU.
 
     python tools/dwbench.py kernel [--batches 64,256] [--out FILE]
+    python tools/dwbench.py kernel --geoms v3_5x5 [...]
     python tools/dwbench.py model  [--batches 64,256] [--out FILE]
 
 `kernel` runs the ten depthwise geometries of MobileNetV2 (224x224 input),
@@ -14,6 +15,10 @@ bf16 and fp32, and times per geometry, alternating in one process:
           streaming yardstick with the same footprint
   island  what a lowered model ran before the kernel existed: ops.to_nchw,
           torch's depthwise conv + BatchNorm + ReLU6 in NCHW, ops.to_nhwc
+
+`--geoms v3_5x5` runs the 5x5 depthwise geometries of MobileNetV3-Large
+instead (its seven 5x5 layers have four distinct geometries), with the
+activation each has there.
 
 `model` measures img/s of MobileNetV2 in bf16 through StageExecutor: the
 zoo's mobilenet_v2() (NHWC input), a torchvision-style torch module lowered
@@ -55,6 +60,11 @@ RING_BYTES = 1 << 30
 GEOMETRIES = [(112, 32, 1), (112, 96, 2), (56, 144, 1), (56, 144, 2),
               (28, 192, 1), (28, 192, 2), (14, 384, 1), (14, 576, 1),
               (14, 576, 2), (7, 960, 1)]
+# (H = W, C, stride, act) of the 5x5 depthwise layers of MobileNetV3-Large:
+# blocks 3; 4 and 5; 12; 13 and 14
+GEOMETRIES_V3_5X5 = [(56, 72, 2, "relu"), (28, 120, 1, "relu"),
+                     (14, 672, 2, "hardswish"), (7, 960, 1, "hardswish")]
+_TORCH_ACTS = {"relu6": nn.ReLU6, "relu": nn.ReLU, "hardswish": nn.Hardswish}
 
 
 def _window_ms(fn, iters):
@@ -97,17 +107,26 @@ def _header(min_window_s=0.1):
 
 
 # ------------------------------------------------------------------ kernel
-def bench_kernel(batches, out):
-    lines = ["Depthwise 3x3 conv + BN + ReLU6 (csrc/dwconv.hip), the ten "
-             "depthwise geometries of",
-             "MobileNetV2. dw GB/s = (input + output + weight bytes) / time, "
-             "1 GB = 1e9 B; dw' is",
-             "the same call as a second contender (run-to-run spread); pool "
-             "= ops.maxpool2d(3, s, 1)",
-             "on the same tensor; island = ops.to_nchw + torch depthwise "
-             "conv + BN + ReLU6 in NCHW +",
-             "ops.to_nhwc. Rings of distinct inputs, inputs + outputs > 1 "
-             "GiB per contender."] + _header()
+def bench_kernel(batches, out, geoms="v2"):
+    if geoms == "v2":
+        R, todo = 3, [g + ("relu6",) for g in GEOMETRIES]
+        what = ["Depthwise 3x3 conv + BN + ReLU6 (csrc/dwconv.hip), the ten "
+                "depthwise geometries of", "MobileNetV2."]
+    else:
+        R, todo = 5, GEOMETRIES_V3_5X5
+        what = ["Depthwise 5x5 conv + BN + ReLU or hardswish "
+                "(csrc/dwconv.hip), the 5x5 depthwise",
+                "geometries of MobileNetV3-Large."]
+    P = R // 2
+    lines = what + [
+        "dw GB/s = (input + output + weight bytes) / time, 1 GB = 1e9 B; "
+        "dw' is the same call",
+        "as a second contender (run-to-run spread); pool = "
+        "ops.maxpool2d(3, s, 1) on the same",
+        "tensor; island = ops.to_nchw + torch depthwise conv + BN + the "
+        "activation in NCHW +",
+        "ops.to_nhwc. Rings of distinct inputs, inputs + outputs > 1 GiB "
+        "per contender."] + _header()
     lines.append(f"{'dtype':<6}{'N':>4} {'HxWxC/s':<14}{'dw ms':>9}"
                  f"{'dw GB/s':>20}{'dw2 ms':>9}{'pool ms':>9}"
                  f"{'island ms':>11}{'isl/dw':>8}{'dw/pool':>9}")
@@ -115,20 +134,21 @@ def bench_kernel(batches, out):
     for dt, dname in ((torch.bfloat16, "bf16"), (torch.float32, "fp32")):
         esz = 2 if dt == torch.bfloat16 else 4
         for nb in batches:
-            for H, C, st in GEOMETRIES:
-                OH = (H + 2 - 3) // st + 1
+            for H, C, st, act in todo:
+                OH = (H + 2 * P - R) // st + 1
                 in_b = nb * H * H * C * esz
                 out_b = nb * OH * OH * C * esz
-                need = in_b + out_b + 9 * C * esz
+                need = in_b + out_b + R * R * C * esz
                 nbuf = max(2, -(-RING_BYTES // (in_b + out_b)))
                 xs = [torch.randn(nb, H, H, C, device=DEV).to(dt)
                       for _ in range(nbuf)]
-                w = (torch.randn(3, 3, C, device=DEV) / 3).to(dt)
+                w = (torch.randn(R, R, C, device=DEV) / R).to(dt)
                 scale = torch.rand(C, device=DEV) + 0.5
                 bias = torch.randn(C, device=DEV) * 0.1
-                conv = nn.Conv2d(C, C, 3, st, 1, groups=C, bias=False)
+                conv = nn.Conv2d(C, C, R, st, P, groups=C, bias=False)
                 bn = nn.BatchNorm2d(C)
-                island = nn.Sequential(conv, bn, nn.ReLU6(inplace=True))
+                island = nn.Sequential(conv, bn,
+                                       _TORCH_ACTS[act](inplace=True))
                 island = island.eval().to(DEV, dt)
                 with torch.no_grad():
                     conv.weight.copy_(w.permute(2, 0, 1).unsqueeze(1))
@@ -141,8 +161,8 @@ def bench_kernel(batches, out):
                     return xs[turn[i]]
 
                 def dw(i=0):
-                    return ops.dwconv2d_bn_act(nxt(i), w, scale, bias, st, 1,
-                                               "relu6")
+                    return ops.dwconv2d_bn_act(nxt(i), w, scale, bias, st, P,
+                                               act)
 
                 def dw2():
                     return dw(1)
@@ -298,6 +318,9 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("what", choices=["kernel", "model"])
     ap.add_argument("--batches", default="64,256")
+    ap.add_argument("--geoms", choices=["v2", "v3_5x5"], default="v2",
+                    help="kernel mode: MobileNetV2's 3x3 geometries or "
+                         "MobileNetV3-Large's 5x5 ones")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -305,7 +328,7 @@ def main():
     batches = [int(b) for b in args.batches.split(",")]
     with torch.no_grad():
         if args.what == "kernel":
-            bench_kernel(batches, args.out)
+            bench_kernel(batches, args.out, args.geoms)
         else:
             bench_model(batches, args.out)
 
