@@ -1031,6 +1031,70 @@ Tensor dwconv2d_bn_act(Tensor x, Tensor w, c10::optional<Tensor> scale,
     return out;
 }
 
+// Grouped 3x3 conv + folded BN + activation (csrc/gconv.hip): x NHWC, w
+// [C, 3, 3, Cg] with Cg = C / groups, both bf16 or both fp32. Everything the
+// kernels do not serve is refused here; there is no other path.
+Tensor gconv2d_bn_act(Tensor x, Tensor w, c10::optional<Tensor> scale,
+                      c10::optional<Tensor> bias, int64_t stride,
+                      int64_t pad, int64_t act) {
+    check_act(act);
+    const bool f32 = is_f32(x, "x");
+    if (f32) {
+        check_f32(x, "x");
+        check_f32(w, "w");
+    } else {
+        check_bf16(x, "x");
+        check_bf16(w, "w");
+        TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 &&
+                    (uintptr_t)w.data_ptr() % 16 == 0,
+                    "x and w must be 16-byte aligned");
+    }
+    TORCH_CHECK(x.dim() == 4, "x must be NHWC");
+    TORCH_CHECK(w.dim() == 4, "w must be [C, 3, 3, Cg]");
+    int64_t NB = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+    int64_t R = w.size(1), S = w.size(2), Cg = w.size(3);
+    TORCH_CHECK(w.size(0) == C, "grouped conv needs Cout == Cin, got w with ",
+                w.size(0), " output channels for x with ", C);
+    TORCH_CHECK(R == 3 && S == 3, "grouped conv needs a 3x3 kernel, got ", R,
+                "x", S);
+    TORCH_CHECK(Cg == 4 || Cg == 8 || Cg == 16 || Cg == 32,
+                "grouped conv needs 4, 8, 16 or 32 channels per group, got ",
+                Cg);
+    TORCH_CHECK(C > 0 && C % 16 == 0 && C % Cg == 0,
+                "grouped conv needs C % 16 == 0 and C % Cg == 0, got C = ",
+                C, " with Cg = ", Cg);
+    TORCH_CHECK(stride == 1 || stride == 2,
+                "grouped conv needs stride 1 or 2, got ", stride);
+    TORCH_CHECK(pad == 0 || pad == 1,
+                "grouped conv needs padding 0 or 1, got ", pad);
+    TORCH_CHECK(H + 2 * pad >= 3 && W + 2 * pad >= 3,
+                "kernel larger than the padded input");
+    TORCH_CHECK(x.numel() < (1LL << 31), "x has 2^31 or more elements");
+    int64_t OH = (H + 2 * pad - 3) / stride + 1;
+    int64_t OW = (W + 2 * pad - 3) / stride + 1;
+    TORCH_CHECK(NB * OH * OW * C < (1LL << 31),
+                "out has 2^31 or more elements");
+    TORCH_CHECK(C <= 64 * 65535, "grouped conv takes at most C = ",
+                64 * 65535, ", got ", C);
+    const float* sc = dw_vec_opt(scale, "scale", ones_buf(), C);
+    const float* bi = dw_vec_opt(bias, "bias", zeros_buf(), C);
+    auto out = at::empty({NB, OH, OW, C}, x.options());
+    if (out.numel() == 0) return out;
+    if (f32)
+        defer_hip::launch_gconv_f32(f32ptr(x), f32ptr(w), sc, bi,
+                                    out.data_ptr<float>(), (int)NB, (int)H,
+                                    (int)W, (int)C, (int)OH, (int)OW,
+                                    (int)Cg, (int)stride, (int)pad, (int)act,
+                                    cur_stream());
+    else
+        defer_hip::launch_gconv(bptr(x), bptr(w), sc, bi, zero_buf(),
+                                bptr_mut(out), (int)NB, (int)H, (int)W,
+                                (int)C, (int)OH, (int)OW, (int)Cg,
+                                (int)stride, (int)pad, (int)act,
+                                cur_stream());
+    return out;
+}
+
 Tensor softmax(Tensor x) {
     if (is_f32(x, "x")) {
         check_f32(x, "x");
@@ -1520,6 +1584,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("stride"), py::arg("pad"), py::arg("act"),
           py::arg("mode") = 0, py::arg("max_blocks") = 0);
     m.def("dwconv2d_bn_act", &dwconv2d_bn_act, py::arg("x"), py::arg("w"),
+          py::arg("scale"), py::arg("bias"), py::arg("stride"),
+          py::arg("pad"), py::arg("act"));
+    m.def("gconv2d_bn_act", &gconv2d_bn_act, py::arg("x"), py::arg("w"),
           py::arg("scale"), py::arg("bias"), py::arg("stride"),
           py::arg("pad"), py::arg("act"));
     m.def("conv_ws_stats", &conv_ws_stats);

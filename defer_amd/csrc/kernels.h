@@ -187,6 +187,20 @@ void launch_dwconv_f32(const float* x, const float* w, const float* scale,
                        int C, int OH, int OW, int R, int stride, int pad,
                        int act, hipStream_t s);
 
+// grouped 3x3 conv + folded BN + activation (gconv.hip), NHWC x and
+// [C][3][3][Cg] w, Cin == Cout == C, C % 16 == 0, C % Cg == 0, Cg in {4, 8,
+// 16, 32}, stride in {1, 2}, pad in {0, 1}; scale and bias non-null fp32[C];
+// act is an ACT_* of common.h. zbuf: >= 16 B of zeros (the bf16 kernel reads
+// padding from it). x and y have fewer than 2^31 elements.
+void launch_gconv(const void* x, const void* w, const float* scale,
+                  const float* bias, const void* zbuf, void* y, int NB, int H,
+                  int W, int C, int OH, int OW, int Cg, int stride, int pad,
+                  int act, hipStream_t s);
+void launch_gconv_f32(const float* x, const float* w, const float* scale,
+                      const float* bias, float* y, int NB, int H, int W,
+                      int C, int OH, int OW, int Cg, int stride, int pad,
+                      int act, hipStream_t s);
+
 // squeeze-excite (se.hip). launch_se_gate: g[n][c] = hardsigmoid(w2 @
 // act(w1 @ mean_hw(x[n]) + b1) + b2), fp32 [NB][C]; x is [NB][HW][C], w1
 // [Cr][C] and w2 [C][Cr] in the compute dtype (f32 ? float : bf16), b1 and

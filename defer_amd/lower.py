@@ -22,6 +22,10 @@ The patterns:
     depthwise Conv2d [+ BatchNorm2d] [+ ReLU | ReLU6 | Hardswish]
         (groups == in == out channels, 3x3 or 5x5, stride 1 or 2,
          padding <= k // 2, C % 8 == 0)            -> DepthwiseConvBNAct
+    grouped Conv2d [+ BatchNorm2d] [+ ReLU | ReLU6 | Hardswish]
+        (1 < groups < C, in == out == C channels, C % 16 == 0, C / groups
+         in {4, 8, 16, 32}, 3x3, stride 1 or 2, padding 0 or 1)
+                                                   -> GroupedConvBNAct
     v * hardsigmoid(conv1x1(relu(conv1x1(pool(v)))))
         (squeeze-excite, see below)                -> SqueezeExcite
     BatchNorm2d [+ ReLU]                           -> BNAct
@@ -36,8 +40,8 @@ The patterns:
     cat over dim 1, flatten into Linear, softmax   -> Concat, Flatten, Softmax
 
 ReLU6 is `nn.ReLU6`, `F.relu6`, `nn.Hardtanh(0., 6.)` or
-`F.hardtanh(x, 0., 6.)`. Every other grouped conv (groups between 1 and C,
-a channel multiplier) stays an island. Hardswish is `nn.Hardswish` or
+`F.hardtanh(x, 0., 6.)`. Every other grouped conv (other group widths, in
+!= out channels, a channel multiplier, other kernels) stays an island. Hardswish is `nn.Hardswish` or
 `F.hardswish`, in place or not.
 
 Squeeze-excite is a `mul` (`a * b`, `torch.mul`, `a.mul(b)`, either operand
@@ -91,6 +95,8 @@ _COUT_VEC = 4       # fp32 conv: Cout % 4; fp32 linear: N % 4
 _MAX_NO_SCALE = 8192    # conv without a scale vector: cached ones[8192]
 _DW_KERNELS = (3, 5)    # depthwise conv (csrc/dwconv.hip): square kernels,
 _DW_STRIDES = (1, 2)    # strides, 0 <= padding <= k // 2, C % _VEC == 0
+_GC_GROUP_CHANNELS = (4, 8, 16, 32)     # grouped 3x3 conv (csrc/gconv.hip):
+_GC_CVEC = 16           # channels per group, C % 16 == 0, in == out == C
 
 
 def _pair(v):
@@ -299,6 +305,26 @@ class _Lowering:
         return None
 
     # ------------------------------------------------------------ patterns
+    @staticmethod
+    def grouped_conv_reason(m) -> Optional[str]:
+        """Why csrc/gconv.hip does not take the grouped conv `m` (1 < groups,
+        not depthwise), or None."""
+        c, cg = m.out_channels, m.in_channels // m.groups
+        if (m.in_channels != c or c % _GC_CVEC
+                or cg not in _GC_GROUP_CHANNELS):
+            return ("besides depthwise convs, only in == out channels with "
+                    f"C % {_GC_CVEC} == 0 and {_GC_GROUP_CHANNELS} channels "
+                    "per group are lowered")
+        pad = None if isinstance(m.padding, str) else _pair(m.padding)
+        if (_pair(m.kernel_size) != (3, 3) or _pair(m.dilation) != (1, 1)
+                or _pair(m.stride) not in ((1, 1), (2, 2))
+                or pad not in ((0, 0), (1, 1))):
+            return (f"kernel={m.kernel_size} stride={m.stride} "
+                    f"padding={m.padding} dilation={m.dilation}: the grouped "
+                    f"kernel takes 3x3 kernels, strides {_DW_STRIDES}, "
+                    "padding 0 or 1 and no dilation")
+        return None
+
     def lower_conv(self, n) -> Optional[str]:
         m = self.mod(n)
         s = self.shape(n.args[0])
@@ -306,10 +332,12 @@ class _Lowering:
             return "Conv2d on a value that is not 4-D"
         depthwise = (m.groups > 1 and m.groups == m.in_channels
                      and m.groups == m.out_channels)
-        if m.groups != 1 and not depthwise:
-            return (f"grouped conv (groups={m.groups}, {m.in_channels} -> "
-                    f"{m.out_channels} channels): only depthwise convs "
-                    "(groups == in == out channels) are lowered")
+        grouped = m.groups != 1 and not depthwise
+        if grouped:
+            why = self.grouped_conv_reason(m)
+            if why is not None:
+                return (f"grouped conv (groups={m.groups}, {m.in_channels} "
+                        f"-> {m.out_channels} channels): {why}")
         if _pair(m.dilation) != (1, 1):
             return f"dilated conv (dilation={tuple(m.dilation)})"
         if m.padding_mode != "zeros":
@@ -357,6 +385,12 @@ class _Lowering:
                                          bn=bn is not None)
             layer.weight = nn.Parameter(                # [C,1,R,S] -> RSC
                 w[:, 0].permute(1, 2, 0).contiguous().float())
+        elif grouped:
+            layer = L.GroupedConvBNAct(m.out_channels, m.groups, stride=st,
+                                       padding=pad, act=act,
+                                       bn=bn is not None)
+            layer.weight = nn.Parameter(        # [C,Cg,3,3] -> [C,3,3,Cg]
+                w.permute(0, 2, 3, 1).contiguous().float())
         else:
             layer = L.ConvBNAct(m.in_channels, m.out_channels, kernel=k,
                                 stride=st, padding=pad, act=act,

@@ -92,6 +92,41 @@ class DepthwiseConvBNAct(nn.Module):
         return 2 * self.kernel * self.kernel * self.c
 
 
+class GroupedConvBNAct(nn.Module):
+    """Grouped 3x3 Conv2d (`groups` groups of c // groups channels, in ==
+    out == c) + folded inference BatchNorm + optional activation, fused:
+    the conv2 of a ResNeXt bottleneck (ops.gconv2d_bn_act; csrc/gconv.hip
+    on the GPU). The weight is [C, 3, 3, Cg] and has 4 dims, so
+    StageExecutor casts it to the compute dtype with the conv weights. Not
+    a ConvBNAct: the fusion passes leave it alone."""
+
+    def __init__(self, c, groups, stride=1, padding=1, act="relu", bn=True):
+        super().__init__()
+        ops._act_code(act)
+        if groups < 1 or c % groups:
+            raise ValueError(f"groups={groups} does not divide c={c}")
+        self.c, self.groups = c, groups
+        self.kernel, self.stride, self.padding = 3, stride, padding
+        self.act = act
+        cg = c // groups
+        w = torch.randn(c, 3, 3, cg) * math.sqrt(2.0 / (9 * cg))
+        self.weight = nn.Parameter(w)
+        self.scale = nn.Parameter(torch.ones(c)) if bn else None
+        self.bias = nn.Parameter(torch.zeros(c))
+
+    def forward(self, x):
+        return ops.gconv2d_bn_act(
+            x, self.weight.to(x.dtype), self.scale, self.bias,
+            stride=self.stride, padding=self.padding, act=self.act)
+
+    def extra_repr(self):
+        return (f"grouped {self.c} g{self.groups} k3 s{self.stride} "
+                f"p{self.padding} act={self.act}")
+
+    def flops_per_pixel(self):
+        return 2 * 9 * (self.c // self.groups) * self.c
+
+
 class SqueezeExcite(nn.Module):
     """Squeeze-excite: x * gate(fc2(act(fc1(mean over H, W of x)))), one
     graph node with one input (ops.squeeze_excite; csrc/se.hip on the GPU).

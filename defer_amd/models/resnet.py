@@ -5,17 +5,21 @@ The reference's benchmark model is Keras ResNet50, include_top=True,
 add_16 so the reference's partition lists (add_2, add_4, ... add_14 —
 test/test.py:18) name the same cut points here. The 101/152 variants
 (deeper conv4_x/conv3_x stages, same bottleneck blocks) exercise the
-partitioner and pipeline at greater depth.
+partitioner and pipeline at greater depth. ResNeXt is the same graph with
+a grouped 3x3 conv2 (GroupedConvBNAct) of width planes * width_per_group //
+64 * groups; node names and add_k cut names are those of the ResNets.
 """
 
 from typing import List
 
 from defer_amd.graph import GraphNode, LayerGraph, GraphModel
 from defer_amd.models.layers import (AddAct, ConvBNAct, Dense,
-                                     GlobalAvgPool, MaxPool, Softmax)
+                                     GlobalAvgPool, GroupedConvBNAct,
+                                     MaxPool, Softmax)
 
 
-def _resnet(depths, name, num_classes=1000, include_top=True) -> GraphModel:
+def _resnet(depths, name, num_classes=1000, include_top=True, groups=1,
+            width_per_group=64) -> GraphModel:
     nodes: List[GraphNode] = []
     add_idx = [0]
 
@@ -29,12 +33,14 @@ def _resnet(depths, name, num_classes=1000, include_top=True) -> GraphModel:
     x = N("pool1", MaxPool(3, 2, 1), [x])
 
     # --- residual stages ----------------------------------------------------
-    def bottleneck(x, stage, block, cin, width, stride):
-        cout = width * 4
+    def bottleneck(x, stage, block, cin, planes, stride):
+        cout = planes * 4
+        width = planes * width_per_group // 64 * groups
         p = f"res{stage}_{block}"
         a = N(f"{p}_conv1", ConvBNAct(cin, width, 1, 1, 0, "relu"), [x])
-        b = N(f"{p}_conv2", ConvBNAct(width, width, 3, stride, 1, "relu"),
-              [a])
+        conv2 = (ConvBNAct(width, width, 3, stride, 1, "relu") if groups == 1
+                 else GroupedConvBNAct(width, groups, stride, 1, "relu"))
+        b = N(f"{p}_conv2", conv2, [a])
         c = N(f"{p}_conv3", ConvBNAct(width, cout, 1, 1, 0, "none"), [b])
         if stride != 1 or cin != cout:
             sc = N(f"{p}_proj", ConvBNAct(cin, cout, 1, stride, 0, "none"),
@@ -72,6 +78,16 @@ def resnet101(num_classes: int = 1000, include_top: bool = True):
 
 def resnet152(num_classes: int = 1000, include_top: bool = True):
     return _resnet((3, 8, 36, 3), "resnet152", num_classes, include_top)
+
+
+def resnext50_32x4d(num_classes: int = 1000, include_top: bool = True):
+    return _resnet((3, 4, 6, 3), "resnext50_32x4d", num_classes,
+                   include_top, groups=32, width_per_group=4)
+
+
+def resnext101_64x4d(num_classes: int = 1000, include_top: bool = True):
+    return _resnet((3, 4, 23, 3), "resnext101_64x4d", num_classes,
+                   include_top, groups=64, width_per_group=4)
 
 
 # The reference's 8-stage partition (7 cuts at every other residual add,

@@ -148,6 +148,66 @@ def dwconv2d_bn_act(x, w, scale=None, bias=None, stride=1, padding=1,
     return m.dwconv2d_bn_act(x, w, scale, bias, stride, padding, code)
 
 
+_GCONV_CG = (4, 8, 16, 32)
+
+
+def _check_gconv(x, w, stride, padding):
+    """The geometry csrc/gconv.hip serves; the same refusals on every
+    device, each naming the value it refuses."""
+    if x.dim() != 4 or w.dim() != 4:
+        raise ValueError(
+            f"gconv2d_bn_act: x must be NHWC and w [C, 3, 3, Cg], got "
+            f"{x.dim()}-D and {w.dim()}-D")
+    c, cg = x.shape[-1], w.shape[-1]
+    if tuple(w.shape[1:3]) != (3, 3):
+        raise ValueError(
+            f"gconv2d_bn_act: needs a 3x3 kernel, got "
+            f"{w.shape[1]}x{w.shape[2]}")
+    if cg not in _GCONV_CG:
+        raise ValueError(
+            f"gconv2d_bn_act: needs {list(_GCONV_CG)} channels per group, "
+            f"got {cg}")
+    if c % 16 or c % cg or w.shape[0] != c:
+        raise ValueError(
+            f"gconv2d_bn_act: needs Cout == Cin == C with C % 16 == 0 and "
+            f"C % Cg == 0, got C = {c}, Cout = {w.shape[0]}, Cg = {cg}")
+    if stride not in (1, 2):
+        raise ValueError(
+            f"gconv2d_bn_act: needs stride 1 or 2, got {stride}")
+    if padding not in (0, 1):
+        raise ValueError(
+            f"gconv2d_bn_act: needs padding 0 or 1, got {padding}")
+    if x.dtype not in (torch.bfloat16, torch.float32) or w.dtype != x.dtype:
+        raise ValueError(
+            f"gconv2d_bn_act: x and w must both be bf16 or both fp32, got "
+            f"{x.dtype} and {w.dtype}")
+
+
+def gconv2d_bn_act(x, w, scale=None, bias=None, stride=1, padding=1,
+                   act="none"):
+    """Grouped 3x3 conv + folded BN + activation, NHWC x and w [C, 3, 3, Cg]
+    (OHWI with I = the channels of one group), groups = C // Cg:
+
+        y[n, oh, ow, k] = act(scale[k] * sum_{r,s,c<Cg} x[n, oh*stride - pad
+                              + r, ow*stride - pad + s, (k // Cg)*Cg + c]
+                              * w[k, r, s, c] + bias[k])
+
+    scale and bias are fp32 [C] (None = 1 / 0); act as in conv2d_bn_act. On
+    the GPU one HIP kernel (csrc/gconv.hip; bf16 on the MFMA) for Cin ==
+    Cout == C, C % 16 == 0, Cg in {4, 8, 16, 32}, stride in {1, 2} and
+    padding in {0, 1}; any other geometry raises, on the CPU too. fp32
+    accumulation in one fixed order, one rounding at the end, run-to-run
+    identical. Non-finite inputs are outside the contract: the bf16 kernel
+    multiplies the other groups' values of a 16-channel slab by zero
+    weights, so an inf in one group can make NaNs in its slab neighbours."""
+    code = _act_code(act)
+    _check_gconv(x, w, stride, padding)
+    m = _backend(x)
+    if m is None:
+        return _ref.gconv2d_bn_act(x, w, scale, bias, stride, padding, act)
+    return m.gconv2d_bn_act(x, w, scale, bias, stride, padding, code)
+
+
 def conv_plan(x_shape, w_shape, stride=1, padding=1, residual=False,
               mode=None, max_blocks=0, variant=None):
     """What conv2d_bn_act (NHWC / OHWI shapes) or linear (2-D shapes) would

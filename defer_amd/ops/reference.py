@@ -96,6 +96,23 @@ def dwconv2d_bn_act(x, w, scale=None, bias=None, stride=1, padding=1,
     return apply_act(y.permute(0, 2, 3, 1), act).to(x.dtype)
 
 
+def gconv2d_bn_act(x, w, scale=None, bias=None, stride=1, padding=1,
+                   act="none"):
+    """Grouped conv + (folded) batchnorm + activation: x [N, H, W, C],
+    w [K, R, S, Cg] with groups = C // Cg (F.conv2d with groups=); output
+    channel k reads the input channels of group k // (K // groups)."""
+    groups = x.shape[-1] // w.shape[-1]
+    xf = x.permute(0, 3, 1, 2).float()                 # NHWC -> NCHW
+    wf = w.permute(0, 3, 1, 2).float()                 # OHWI -> OIHW
+    y = F.conv2d(xf, wf, bias=None, stride=stride, padding=padding,
+                 groups=groups)
+    if scale is not None:
+        y = y * scale.float().view(1, -1, 1, 1)
+    if bias is not None:
+        y = y + bias.float().view(1, -1, 1, 1)
+    return apply_act(y.permute(0, 2, 3, 1), act).to(x.dtype)
+
+
 def batchnorm_apply(x, scale, bias, act="none"):
     """Standalone inference batchnorm (y = x*scale + bias), NHWC.
 

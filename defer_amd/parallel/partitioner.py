@@ -134,6 +134,11 @@ def node_times(graph: LayerGraph, input_shape=(1, 224, 224, 3),
             # kernels' rate
             f = float(out[0] * out[1] * out[2]) * lay.flops_per_pixel()
             t = (in_b + out_b) / _BW_ELTW
+        elif isinstance(lay, L.GroupedConvBNAct):
+            # the MFMA kernel of csrc/gconv.hip: the useful flops at the 3x3
+            # rate or, far more often, one pass over input and output
+            f = float(out[0] * out[1] * out[2]) * lay.flops_per_pixel()
+            t = max(f / _EFF_3X3, (in_b + out_b) / _BW_STREAM)
         elif isinstance(lay, L.SqueezeExcite):
             # three passes over the tensor at the streaming kernels' rate:
             # the pool reads it, the scale pass reads it again and writes
