@@ -1031,6 +1031,147 @@ Tensor dwconv2d_bn_act(Tensor x, Tensor w, c10::optional<Tensor> scale,
     return out;
 }
 
+// x of the channel-vector ops: bf16 or fp32, contiguous, 16-byte aligned,
+// C a multiple of one vector. Returns true for fp32.
+bool check_channel_vec(const Tensor& x, const char* op) {
+    const bool f32 = is_f32(x, "x");
+    TORCH_CHECK(x.is_cuda(), op, ": x must be on GPU");
+    TORCH_CHECK(x.is_contiguous(), op, ": x must be contiguous");
+    TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0, op,
+                ": x must be 16-byte aligned");
+    const int vec = f32 ? 4 : 8;
+    const int64_t C = x.size(-1);
+    TORCH_CHECK(C > 0 && C % vec == 0, op, ": ", f32 ? "fp32" : "bf16",
+                " needs C % ", vec, " == 0 (16-byte channel vectors), got "
+                "C = ", C);
+    return f32;
+}
+
+const float* channel_vec_param(const Tensor& t, const char* op,
+                               const char* name, int64_t C) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat &&
+                t.is_contiguous() && t.dim() == 1 && t.numel() == C,
+                op, ": ", name, " must be a contiguous GPU fp32[C] with C = ",
+                C);
+    return t.data_ptr<float>();
+}
+
+// 7x7 depthwise conv, stride 1, padding 3, + bias (csrc/dwconv7.hip): x
+// NHWC, w [7, 7, C], both bf16 or both fp32. max_blocks caps the grid along
+// the tiles (0 = policy).
+Tensor dwconv7x7(Tensor x, Tensor w, c10::optional<Tensor> bias,
+                 int64_t max_blocks) {
+    TORCH_CHECK(x.dim() == 4, "dwconv7x7: x must be NHWC");
+    TORCH_CHECK(w.dim() == 3, "dwconv7x7: w must be [7, 7, C]");
+    const bool f32 = check_channel_vec(x, "dwconv7x7");
+    TORCH_CHECK(w.is_cuda() && w.scalar_type() == x.scalar_type() &&
+                w.is_contiguous() && (uintptr_t)w.data_ptr() % 16 == 0,
+                "dwconv7x7: w must be a contiguous GPU tensor of x's dtype "
+                "(mixed dtypes)");
+    int64_t NB = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+    TORCH_CHECK(w.size(0) == 7 && w.size(1) == 7 && w.size(2) == C,
+                "dwconv7x7: w must be [7, 7, C] with C = ", C);
+    TORCH_CHECK(max_blocks >= 0, "max_blocks must be >= 0");
+    TORCH_CHECK(H * W * C < (1LL << 31),
+                "dwconv7x7: an image has 2^31 or more elements");
+    const float* bi;
+    if (bias) {
+        bi = channel_vec_param(*bias, "dwconv7x7", "bias", C);
+    } else {
+        TORCH_CHECK(C <= 8192, "dwconv7x7 without bias takes at most "
+                    "C = 8192, got ", C);
+        bi = zeros_buf();
+    }
+    auto out = at::empty_like(x);
+    if (out.numel() == 0) return out;
+    defer_hip::launch_dwconv7(bptr(x), bptr(w), bi, bptr_mut(out), (int)NB,
+                              (int)H, (int)W, (int)C, f32, (int)max_blocks,
+                              cur_stream());
+    return out;
+}
+
+// What dwconv7x7 launches for an NHWC shape: the tile policy of dw7_geom.
+// Needs no GPU.
+py::dict dwconv7x7_plan(std::vector<int64_t> xs, bool f32) {
+    using namespace pybind11::literals;
+    TORCH_CHECK(xs.size() == 4, "x must be NHWC");
+    const auto g = defer_hip::dw7_geom((int)xs[0], (int)xs[1], (int)xs[2],
+                                       (int)xs[3], f32 ? 4 : 8);
+    return py::dict("TH"_a = g.TH, "TW"_a = g.TW, "nth"_a = g.nth,
+                    "ntw"_a = g.ntw, "CBV"_a = g.CBV, "PV"_a = g.PV,
+                    "ncb"_a = g.ncb, "lds_bytes"_a = g.lds_bytes,
+                    "tiles"_a = g.tiles);
+}
+
+// LayerNorm over the last dim (csrc/layernorm.hip): x of rank >= 2, weight
+// and bias fp32[C]. max_blocks caps the grid (0 = policy).
+Tensor layernorm_channels(Tensor x, Tensor weight, Tensor bias, double eps,
+                          int64_t max_blocks) {
+    TORCH_CHECK(x.dim() >= 2, "layernorm_channels: x must have rank >= 2");
+    const bool f32 = check_channel_vec(x, "layernorm_channels");
+    const int64_t C = x.size(-1);
+    TORCH_CHECK(C <= defer_hip::LAYERNORM_MAX_C,
+                "layernorm_channels: needs C <= ", defer_hip::LAYERNORM_MAX_C,
+                ", got C = ", C);
+    TORCH_CHECK(max_blocks >= 0, "max_blocks must be >= 0");
+    const float* wt = channel_vec_param(weight, "layernorm_channels",
+                                        "weight", C);
+    const float* bi = channel_vec_param(bias, "layernorm_channels", "bias",
+                                        C);
+    auto out = at::empty_like(x);
+    if (out.numel() == 0) return out;
+    defer_hip::launch_layernorm(bptr(x), wt, bi, bptr_mut(out),
+                                x.numel() / C, (int)C, (float)eps, f32,
+                                (int)max_blocks, cur_stream());
+    return out;
+}
+
+// gelu(x[M, K] @ w[N, K]^T + bias): linear with the GELU epilogue. bf16: the
+// GEMM-mode plan of linear, run on its ACT_GELU instantiation; fp32: the
+// runtime act of conv_f32_kernel. The shape rules are linear's.
+Tensor linear_gelu(Tensor x, Tensor w, c10::optional<Tensor> bias) {
+    TORCH_CHECK(x.dim() == 2 && w.dim() == 2, "linear_gelu wants 2-D");
+    const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+    TORCH_CHECK(w.size(1) == K, "K mismatch");
+    TORCH_CHECK(M < (1LL << 31), "M too large");
+    auto out = at::empty({M, N}, x.options());
+    c10::optional<Tensor> bias_f;
+    if (bias) {
+        TORCH_CHECK(bias->is_cuda() && bias->numel() == N,
+                    "linear_gelu: bias must be a GPU tensor of Cout = ", N,
+                    " values");
+        bias_f = bias->scalar_type() == at::kFloat && bias->is_contiguous()
+                     ? *bias
+                     : cached_weight_prep(*bias, -1, [&] {
+                           return bias->to(at::kFloat).contiguous();
+                       });
+    }
+    if (is_f32(x, "x")) {
+        check_f32(x, "x");
+        check_f32(w, "w");
+        TORCH_CHECK(K % 4 == 0, "fp32 linear_gelu needs K % 4 == 0, got ", K);
+        TORCH_CHECK(N % 4 == 0, "fp32 linear_gelu needs N % 4 == 0, got ", N);
+        run_conv_f32(x, w, nullptr, f32_vec_opt(bias_f, "bias", N),
+                     c10::nullopt, out, M, 1, 1, (int)K, 1, 1, 1, 1, 1, 0,
+                     /* ACT_GELU of common.h */ 4);
+        return out;
+    }
+    check_bf16(x, "x");
+    check_bf16(w, "w");
+    TORCH_CHECK(K % 8 == 0, "K must be a multiple of 8");
+    if (M == 0) return out;
+    ConvParams p = conv_geom(M, (int)K, (int)N, 0, 0, 0, 0, 0, 0, 1, 1, 1, 0,
+                             true);
+    p.x = bptr(x); p.w = bptr(w);
+    p.scale = fptr_opt(c10::nullopt, "scale", ones_buf(), N);
+    p.bias = fptr_opt(bias_f, "bias", zeros_buf(), N);
+    p.res = nullptr; p.out = bptr_mut(out); p.zbuf = zero_buf();
+    const auto plan = defer_hip::plan_conv(p, true, false, 2, 0,
+                                           defer_hip::conv_variant());
+    defer_hip::launch_gemm_gelu(p, plan, cur_stream());
+    return out;
+}
+
 // Grouped 3x3 conv + folded BN + activation (csrc/gconv.hip): x NHWC, w
 // [C, 3, 3, Cg] with Cg = C / groups, both bf16 or both fp32. Everything the
 // kernels do not serve is refused here; there is no other path.
@@ -1589,6 +1730,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gconv2d_bn_act", &gconv2d_bn_act, py::arg("x"), py::arg("w"),
           py::arg("scale"), py::arg("bias"), py::arg("stride"),
           py::arg("pad"), py::arg("act"));
+    m.def("dwconv7x7", &dwconv7x7, py::arg("x"), py::arg("w"),
+          py::arg("bias"), py::arg("max_blocks") = 0);
+    m.def("dwconv7x7_plan", &dwconv7x7_plan, py::arg("x_shape"),
+          py::arg("f32") = false);
+    m.def("layernorm_channels", &layernorm_channels, py::arg("x"),
+          py::arg("weight"), py::arg("bias"), py::arg("eps"),
+          py::arg("max_blocks") = 0);
+    m.def("layernorm_plan", [](int64_t C, bool f32) {
+        const auto pl = defer_hip::layernorm_plan((int)C, f32 ? 4 : 8);
+        return std::make_pair(pl.G, pl.VPL);
+    }, py::arg("C"), py::arg("f32") = false);
+    m.def("linear_gelu", &linear_gelu, py::arg("x"), py::arg("w"),
+          py::arg("bias"));
     m.def("conv_ws_stats", &conv_ws_stats);
     m.def("conv_plan", &conv_plan, py::arg("x_shape"), py::arg("w_shape"),
           py::arg("stride"), py::arg("pad"), py::arg("has_res"),

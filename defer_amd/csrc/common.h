@@ -42,6 +42,17 @@ __device__ __forceinline__ int cdiv(int a, int b) { return (a + b - 1) / b; }
 // of the bindings; the bf16 conv templates take ACT_RELU with a bound for
 // it, and ACT_NONE, ACT_RELU or ACT_HARDSWISH as their ACT)
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_RELU6 = 2, ACT_HARDSWISH = 3 };
+// the exact GELU of linear_gelu. Not a value of the ops' `act`: only the
+// GEMM-mode instantiations behind launch_gemm_gelu and launch_conv_f32's
+// caller in that binding name it.
+enum { ACT_GELU = 4 };
+
+// gelu(v) = 0.5 * v * (1 + erf(v / sqrt(2))), in this order everywhere
+// (ops/reference.py too); erff(v * 0.70710678f) is 1 in fp32 from about
+// v = 5.6, so gelu returns v bit for bit from there.
+__device__ __forceinline__ float gelu_f(float v) {
+    return 0.5f * v * (1.0f + erff(v * 0.70710678f));
+}
 
 // hardsigmoid(v) = min(max(v + 3, 0), 6) * (1/6), hardswish(v) = v * that,
 // in this order everywhere (ops/reference.py too): 6 * c6 and 3 * c6 round
@@ -62,10 +73,12 @@ __device__ __forceinline__ float apply_act(float v, int act) {
 // plain ReLU (min(v, +inf) == v, so the bits are those of apply_act) and
 // hi = 6 is ReLU6, without a third template value per kernel. ACT_HARDSWISH
 // is a template value of its own: as a runtime flag inside the ReLU
-// instantiations it cost ResNet50 2.5 % (docs/OPTIMIZATION_LOG.md). act is a
+// instantiations it cost ResNet50 2.5 % (docs/OPTIMIZATION_LOG.md); ACT_GELU
+// likewise, for the GEMM-mode kernels only (conv.hip, gelu_rows). act is a
 // compile-time constant at every call, so the ReLU and no-activation
 // instantiations are what they were.
 __device__ __forceinline__ float apply_act_hi(float v, int act, float hi) {
     if (act == ACT_HARDSWISH) return hardswish_f(v);
+    if (act == ACT_GELU) return gelu_f(v);
     return act == ACT_RELU ? fminf(fmaxf(v, 0.0f), hi) : v;
 }

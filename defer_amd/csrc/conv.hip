@@ -1335,6 +1335,50 @@ void launch_conv_igemm(const ConvParams& p0, const ConvPlan& pl, int act,
                        dim3(pl.grid_x, pl.grid_y), dim3(NTHREADS), 0, s, p);
 }
 
+// The GELU epilogue (linear_gelu): one instantiation per GEMM-mode row of
+// conv_rows, without a residual, in a table of its own so that conv_rows and
+// its kernels stay what they were. The keys are the rows' (plan_key).
+struct GeluRow {
+    std::array<int, 7> key;
+    ConvKernel kernel;
+};
+#define GELU_ROW(...)                                                     \
+    {{{AMODE_GEMM, __VA_ARGS__}},                                         \
+     conv_igemm_kernel<ACT_GELU, false, AMODE_GEMM, __VA_ARGS__>}
+static const GeluRow gelu_rows[] = {
+    //       bp,   BM,  BN, DA, DB, WPS
+    GELU_ROW(true, 128, 64, 4, 2, 2),
+    GELU_ROW(false, 128, 64, 3, 3, 2),
+    GELU_ROW(true, 128, 64, 3, 3, 2),    // legacy
+    GELU_ROW(false, 128, 128, 2, 2, 2),
+    GELU_ROW(false, 64, 128, 3, 3, 2),
+    GELU_ROW(true, 64, 64, 4, 2, 4),
+    GELU_ROW(false, 64, 64, 3, 3, 3),
+    GELU_ROW(true, 64, 64, 4, 2, 2),
+    GELU_ROW(false, 64, 64, 3, 3, 2),
+    GELU_ROW(true, 64, 64, 3, 3, 2),     // legacy
+};
+
+void launch_gemm_gelu(const ConvParams& p0, const ConvPlan& pl,
+                      hipStream_t s) {
+    if (pl.family != ConvPlan::IGEMM || pl.amode != AMODE_GEMM)
+        throw std::runtime_error("launch_gemm_gelu: not a GEMM-mode plan: " +
+                                 to_string(pl));
+    ConvParams p = p0;
+    p.owmul = magic32((u32)p.OW);
+    p.ohmul = magic32((u32)p.OH);
+    p.cmul = magic32((u32)p.Cin);
+    p.smul = magic32((u32)p.S);
+    for (const GeluRow& r : gelu_rows)
+        if (r.key == plan_key(pl)) {
+            hipLaunchKernelGGL(r.kernel, dim3(pl.grid_x, pl.grid_y),
+                               dim3(NTHREADS), 0, s, p);
+            return;
+        }
+    throw std::runtime_error("no GELU kernel for this plan: " +
+                             to_string(pl));
+}
+
 static int grid1d(long work, int block) {
     long g = (work + block - 1) / block;
     return (int)(g < 2048 ? g : 2048);

@@ -229,6 +229,9 @@ __global__ __launch_bounds__(F32_TPB) void conv_f32_kernel(
         if (p.relu == ACT_HARDSWISH) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = hardswish_f(v[e]);
+        } else if (p.relu == ACT_GELU) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = gelu_f(v[e]);
         } else if (p.relu) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);

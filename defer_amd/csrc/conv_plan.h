@@ -306,6 +306,12 @@ inline ConvPlan plan_conv(const ConvParams& p, bool gemm_mode,
 // hardswish (a bool gives none / relu).
 void launch_conv_igemm(const ConvParams& p, const ConvPlan& plan, int act,
                        bool has_res, hipStream_t s);
+// out = gelu(x[M,K] @ w[N,K]^T * scale + bias), the exact GELU (gelu_f of
+// common.h) in the epilogue of the GEMM-mode kernels: the plan must be
+// plan_conv's for gemm_mode, every such plan has an instantiation, any other
+// throws. No residual.
+void launch_gemm_gelu(const ConvParams& p, const ConvPlan& plan,
+                      hipStream_t s);
 // weight-stationary window kernel (conv_ws.hip): 3x3/s1/p1 convs with
 // Cin = Cout = 64 keep the whole weight tensor in registers and stage only
 // input windows to LDS; bit-identical to launch_conv_igemm on the same

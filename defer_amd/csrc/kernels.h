@@ -142,7 +142,8 @@ struct ConvF32Params {
     int M, K, Cout;
     int H, W, Cin;
     int OH, OW, S, stride, pad;
-    int relu;           // an ACT_* of common.h, ACT_HARDSWISH included
+    int relu;           // an ACT_* of common.h, ACT_HARDSWISH included;
+                        // ACT_GELU from the linear_gelu binding alone
 };
 // tile: 0 = heuristic, 1 = 128x128, 2 = 128x64 (A/B measurement switch)
 void launch_conv_f32(const ConvF32Params& p, bool gemm_mode, int tile,
@@ -186,6 +187,37 @@ void launch_dwconv_f32(const float* x, const float* w, const float* scale,
                        const float* bias, float* y, int NB, int H, int W,
                        int C, int OH, int OW, int R, int stride, int pad,
                        int act, hipStream_t s);
+
+// 7x7 depthwise conv, stride 1, padding 3, + bias (dwconv7.hip): NHWC x, w
+// [7][7][C], bias non-null fp32[C], y of x's shape; C % 8 == 0 (bf16) or
+// C % 4 == 0 (fp32), H * W * C < 2^31 (offsets inside an image are 32-bit).
+// dw7_geom is the tile policy, a pure function of the shape (vec = channels
+// per 16-byte vector): a TH x TW tile of one image times CBV channel vectors
+// per workgroup, PV the padded pixel pitch in LDS, in vectors.
+struct Dw7Geom {
+    int N, H, W, C;
+    int TH, TW, nth, ntw;   // tile rows / columns, tiles per image each way
+    int CBV, PV, ncb;       // channel vectors per block, LDS pitch, blocks
+    int lds_bytes;          // window + weights, dynamic LDS of the launch
+    long tiles;             // N * nth * ntw
+};
+Dw7Geom dw7_geom(int NB, int H, int W, int C, int vec);
+// max_blocks caps the grid along the tiles (0 = policy)
+void launch_dwconv7(const void* x, const void* w, const float* bias, void* y,
+                    int NB, int H, int W, int C, bool f32, int max_blocks,
+                    hipStream_t s);
+
+// LayerNorm over the last dim (layernorm.hip): x and y [rows][C] in the
+// compute dtype, weight and bias fp32[C]; C % 8 == 0 (bf16) or C % 4 == 0
+// (fp32), C <= LAYERNORM_MAX_C. layernorm_plan: G lanes own a row, VPL
+// 16-byte vectors each (G == 0: no kernel for this C).
+constexpr int LAYERNORM_MAX_C = 2048;
+struct LnPlan { int G, VPL; };
+LnPlan layernorm_plan(int C, int vec);
+// max_blocks caps the grid (0 = policy)
+void launch_layernorm(const void* x, const float* weight, const float* bias,
+                      void* y, long rows, int C, float eps, bool f32,
+                      int max_blocks, hipStream_t s);
 
 // grouped 3x3 conv + folded BN + activation (gconv.hip), NHWC x and
 // [C][3][3][Cg] w, Cin == Cout == C, C % 16 == 0, C % Cg == 0, Cg in {4, 8,

@@ -1,6 +1,7 @@
 from defer_amd.models.resnet import (DEFER_8STAGE_CUTS, resnet50,  # noqa: F401
                                      resnet101, resnet152,
                                      resnext50_32x4d, resnext101_64x4d)
+from defer_amd.models.convnext import convnext_tiny  # noqa: F401
 from defer_amd.models.densenet import densenet121  # noqa: F401
 from defer_amd.models.mobilenet import (mobilenet_v2,  # noqa: F401
                                         mobilenet_v3_large)
@@ -11,4 +12,5 @@ MODELS = {"resnet50": resnet50, "resnet101": resnet101,
           "resnext101_64x4d": resnext101_64x4d, "vgg19": vgg19,
           "vgg19_gap": vgg19_gap, "densenet121": densenet121,
           "mobilenetv2": mobilenet_v2,
-          "mobilenetv3large": mobilenet_v3_large}
+          "mobilenetv3large": mobilenet_v3_large,
+          "convnext_tiny": convnext_tiny}

@@ -92,6 +92,69 @@ class DepthwiseConvBNAct(nn.Module):
         return 2 * self.kernel * self.kernel * self.c
 
 
+class DepthwiseConv7x7(nn.Module):
+    """7x7 depthwise Conv2d, stride 1, padding 3, with a bias and nothing
+    after it: the first layer of a ConvNeXt block (ops.dwconv7x7;
+    csrc/dwconv7.hip on the GPU). The weight is [7, 7, C] and has 3 dims, so
+    StageExecutor casts it to the compute dtype with the conv weights."""
+
+    def __init__(self, c):
+        super().__init__()
+        self.c = c
+        self.weight = nn.Parameter(torch.randn(7, 7, c) * math.sqrt(1.0 / 49))
+        self.bias = nn.Parameter(torch.zeros(c))
+
+    def forward(self, x):
+        return ops.dwconv7x7(x, self.weight.to(x.dtype), self.bias)
+
+    def extra_repr(self):
+        return f"depthwise {self.c} k7 s1 p3"
+
+    def flops_per_pixel(self):
+        return 2 * 49 * self.c
+
+
+class LayerNormC(nn.Module):
+    """LayerNorm over the channel (last) dim of an NHWC or [N, C] tensor
+    (ops.layernorm_channels; csrc/layernorm.hip on the GPU). weight and bias
+    are 1-D and stay fp32."""
+
+    def __init__(self, c, eps=1e-6):
+        super().__init__()
+        self.c, self.eps = c, eps
+        self.weight = nn.Parameter(torch.ones(c))
+        self.bias = nn.Parameter(torch.zeros(c))
+
+    def forward(self, x):
+        return ops.layernorm_channels(x, self.weight, self.bias, self.eps)
+
+    def extra_repr(self):
+        return f"layernorm {self.c} eps={self.eps}"
+
+
+class PointwiseGelu(nn.Module):
+    """Linear over the channel dim + exact GELU, fused (ops.linear_gelu): the
+    expanding pointwise layer of a ConvNeXt block. The weight is [Cout, Cin],
+    2-D, so StageExecutor casts it to the compute dtype; the bias stays
+    fp32."""
+
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.cin, self.cout = cin, cout
+        self.weight = nn.Parameter(
+            torch.randn(cout, cin) * math.sqrt(2.0 / cin))
+        self.bias = nn.Parameter(torch.zeros(cout))
+
+    def forward(self, x):
+        return ops.linear_gelu(x, self.weight.to(x.dtype), self.bias)
+
+    def extra_repr(self):
+        return f"{self.cin}->{self.cout} k1 gelu"
+
+    def flops_per_pixel(self):
+        return 2 * self.cin * self.cout
+
+
 class GroupedConvBNAct(nn.Module):
     """Grouped 3x3 Conv2d (`groups` groups of c // groups channels, in ==
     out == c) + folded inference BatchNorm + optional activation, fused:

@@ -148,6 +148,122 @@ def dwconv2d_bn_act(x, w, scale=None, bias=None, stride=1, padding=1,
     return m.dwconv2d_bn_act(x, w, scale, bias, stride, padding, code)
 
 
+_VEC_DTYPES = {torch.bfloat16: 8, torch.float32: 4}
+
+
+def _check_channel_vec(name, x, params, c_max=None):
+    """The rules the 16-byte-vector kernels share, for every device: x is a
+    contiguous bf16 or fp32 tensor whose channel count is a multiple of one
+    vector, and every fp32 [C] parameter lives on x's device. Each refusal
+    names its rule."""
+    if x.dtype not in _VEC_DTYPES:
+        raise RuntimeError(f"{name}: x must be bf16 or fp32, got {x.dtype}")
+    if not x.is_contiguous():
+        raise RuntimeError(f"{name}: x must be contiguous")
+    c, vec = x.shape[-1], _VEC_DTYPES[x.dtype]
+    if c == 0 or c % vec:
+        raise RuntimeError(
+            f"{name}: {x.dtype} needs C % {vec} == 0 (16-byte channel "
+            f"vectors), got C = {c}")
+    if c_max is not None and c > c_max:
+        raise RuntimeError(f"{name}: needs C <= {c_max}, got C = {c}")
+    for pname, p in params:
+        if p is None:
+            continue
+        if p.device != x.device:
+            raise RuntimeError(
+                f"{name}: {pname} must be on x's device {x.device}, got "
+                f"{p.device}")
+        if (p.dtype != torch.float32 or not p.is_contiguous()
+                or tuple(p.shape) != (c,)):
+            raise RuntimeError(
+                f"{name}: {pname} must be a contiguous fp32[C] with C = {c}, "
+                f"got {p.dtype} {tuple(p.shape)}")
+
+
+def dwconv7x7(x, w, bias=None, max_blocks=0):
+    """7x7 depthwise conv, stride 1, padding 3, NHWC x and [7, 7, C] w in
+    x's dtype, fp32 bias [C] or None; the output has x's shape:
+
+        y[n, oh, ow, c] = sum_{r,s} x[n, oh-3+r, ow-3+s, c] * w[r, s, c]
+                          + bias[c]
+
+    No scale and no activation (ConvNeXt has neither here). On the GPU one
+    HIP kernel (csrc/dwconv7.hip) that stages each tile's window and the
+    weights in LDS; C % 8 == 0 (bf16) or C % 4 == 0 (fp32), anything else
+    raises, on the CPU too. fp32 fmaf in the fixed tap order (r, then s),
+    one rounding, run-to-run identical. N == 0 gives an empty tensor.
+    max_blocks caps the grid along the tiles (0 = policy), so a few
+    workgroups walk many tiles."""
+    if x.dim() != 4 or w.dim() != 3:
+        raise RuntimeError(
+            f"dwconv7x7: x must be NHWC (4-D) and w [7, 7, C] (3-D), got "
+            f"{x.dim()}-D and {w.dim()}-D")
+    if w.dtype != x.dtype:
+        raise RuntimeError(
+            f"dwconv7x7: w must be {x.dtype} like x (mixed dtypes), got "
+            f"{w.dtype}")
+    _check_channel_vec("dwconv7x7", x, (("bias", bias),))
+    if tuple(w.shape) != (7, 7, x.shape[-1]):
+        raise RuntimeError(
+            f"dwconv7x7: w must be [7, 7, C] with C = {x.shape[-1]}, got "
+            f"{tuple(w.shape)}")
+    if w.device != x.device or not w.is_contiguous():
+        raise RuntimeError(
+            f"dwconv7x7: w must be contiguous on x's device {x.device}")
+    m = _backend(x)
+    if m is None:
+        return _ref.dwconv7x7(x, w, bias)
+    return m.dwconv7x7(x, w, bias, max_blocks)
+
+
+LAYERNORM_MAX_C = 2048
+
+
+def layernorm_channels(x, weight, bias, eps=1e-6, max_blocks=0):
+    """LayerNorm over the last (channel) dim of a contiguous x of rank >= 2,
+    per leading index, with fp32 weight and bias [C]:
+
+        y[..., c] = (x[..., c] - mean) / sqrt(var + eps) * weight[c] + bias[c]
+
+    var is the biased variance. On the GPU one HIP kernel (csrc/layernorm.hip):
+    a row is read once, kept in registers and written once; mean, then the
+    sum of squared differences from it, in fp32 by xor-shuffle trees; one
+    rounding. C % 8 == 0 (bf16) or C % 4 == 0 (fp32) and C <= 2048, anything
+    else raises, on the CPU too. No host sync. max_blocks caps the grid (0 =
+    policy)."""
+    if x.dim() < 2:
+        raise RuntimeError(
+            f"layernorm_channels: x must have rank >= 2, got {x.dim()}-D")
+    _check_channel_vec("layernorm_channels", x,
+                       (("weight", weight), ("bias", bias)), LAYERNORM_MAX_C)
+    m = _backend(x)
+    if m is None:
+        return _ref.layernorm_channels(x, weight, bias, eps)
+    return m.layernorm_channels(x, weight, bias, eps, max_blocks)
+
+
+def linear_gelu(x, w, bias=None):
+    """gelu(x @ w.T + bias) for x [..., Cin] and w [Cout, Cin]: the exact
+    (erf) GELU, 0.5 * v * (1 + erf(v * 0.70710678)), in fp32 before the one
+    rounding. On the GPU the GEMM-mode kernels of linear and the 1x1 convs
+    with a GELU epilogue (bf16: instantiations of their own in csrc/conv.hip;
+    fp32: the runtime act of csrc/conv_f32.hip), with their shape rules:
+    Cin % 8 == 0 (bf16) or Cin % 4 == 0 and Cout % 4 == 0 (fp32). This is the
+    only way to a GELU: no op takes it as an `act`."""
+    if x.dim() < 1 or w.dim() != 2 or w.shape[1] != x.shape[-1]:
+        raise RuntimeError(
+            f"linear_gelu: x must be [..., Cin] and w [Cout, Cin], got "
+            f"{tuple(x.shape)} and {tuple(w.shape)}")
+    m = _backend(x)
+    if m is None:
+        return _ref.linear_gelu(x, w, bias)
+    if not x.is_contiguous():
+        raise RuntimeError("linear_gelu: x must be contiguous")
+    y = m.linear_gelu(x.reshape(-1, x.shape[-1]), w, bias)
+    return y.reshape(*x.shape[:-1], w.shape[0])
+
+
 _GCONV_CG = (4, 8, 16, 32)
 
 

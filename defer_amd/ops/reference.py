@@ -113,6 +113,46 @@ def gconv2d_bn_act(x, w, scale=None, bias=None, stride=1, padding=1,
     return apply_act(y.permute(0, 2, 3, 1), act).to(x.dtype)
 
 
+def dwconv7x7(x, w, bias=None):
+    """7x7 depthwise conv, stride 1, padding 3: x [N, H, W, C], w [7, 7, C],
+    bias fp32 [C] or None; no scale and no activation.
+
+    y[n, oh, ow, c] = sum_{r,s} x[n, oh-3+r, ow-3+s, c] * w[r, s, c] + bias[c]"""
+    c = x.shape[-1]
+    xf = x.permute(0, 3, 1, 2).float()                 # NHWC -> NCHW
+    wf = w.permute(2, 0, 1).unsqueeze(1).float()       # RSC -> [C, 1, R, S]
+    y = F.conv2d(xf, wf, bias=None, stride=1, padding=3, groups=c)
+    if bias is not None:
+        y = y + bias.float().view(1, -1, 1, 1)
+    return y.permute(0, 2, 3, 1).contiguous().to(x.dtype)
+
+
+def layernorm_channels(x, weight, bias, eps=1e-6):
+    """LayerNorm over the last dim, per leading index, in fp32 with the
+    biased variance taken from the differences to the mean (two passes):
+
+    y[..., c] = (x[..., c] - mean) / sqrt(var + eps) * weight[c] + bias[c]"""
+    xf = x.float()
+    d = xf - xf.mean(dim=-1, keepdim=True)
+    var = (d * d).mean(dim=-1, keepdim=True)
+    y = d * (1.0 / torch.sqrt(var + eps)) * weight.float() + bias.float()
+    return y.to(x.dtype)
+
+
+def _gelu_f32(v: torch.Tensor) -> torch.Tensor:
+    """The exact (erf) GELU of an fp32 tensor, in the kernels' order."""
+    return 0.5 * v * (1.0 + torch.erf(v * 0.70710678))
+
+
+def linear_gelu(x, w, bias=None):
+    """gelu(x @ w^T + bias): x [..., Cin], w [Cout, Cin]; the exact GELU in
+    fp32 before the one rounding."""
+    y = x.float() @ w.float().t()
+    if bias is not None:
+        y = y + bias.float()
+    return _gelu_f32(y).to(x.dtype)
+
+
 def batchnorm_apply(x, scale, bias, act="none"):
     """Standalone inference batchnorm (y = x*scale + bias), NHWC.
 

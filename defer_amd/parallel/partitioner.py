@@ -134,6 +134,19 @@ def node_times(graph: LayerGraph, input_shape=(1, 224, 224, 3),
             # kernels' rate
             f = float(out[0] * out[1] * out[2]) * lay.flops_per_pixel()
             t = (in_b + out_b) / _BW_ELTW
+        elif isinstance(lay, L.DepthwiseConv7x7):
+            # window and weights in LDS, every input element read once per
+            # tile: one pass over input and output at the streaming rate
+            f = float(out[0] * out[1] * out[2]) * lay.flops_per_pixel()
+            t = (in_b + out_b) / _BW_ELTW
+        elif isinstance(lay, L.LayerNormC):
+            # a row is read once, kept in registers and written once
+            f = 8.0 * float(torch.tensor(out).prod())
+            t = (in_b + out_b) / _BW_ELTW
+        elif isinstance(lay, L.PointwiseGelu):
+            # a GEMM-mode 1x1 conv with another epilogue
+            f = float(torch.tensor(out[:-1]).prod()) * lay.flops_per_pixel()
+            t = max(f / _EFF_1X1, (in_b + out_b) / _BW_STREAM)
         elif isinstance(lay, L.GroupedConvBNAct):
             # the MFMA kernel of csrc/gconv.hip: the useful flops at the 3x3
             # rate or, far more often, one pass over input and output
