@@ -1126,6 +1126,94 @@ Tensor layernorm_channels(Tensor x, Tensor weight, Tensor bias, double eps,
     return out;
 }
 
+// Fused multi-head attention (csrc/attention.hip): qkv [..., T, 3 * C] with
+// the last dim laid out [3][heads][64], out [..., T, C].
+Tensor attention(Tensor qkv, int64_t heads) {
+    TORCH_CHECK(qkv.is_cuda(), "attention: qkv must be on GPU");
+    TORCH_CHECK(qkv.scalar_type() == at::kBFloat16 ||
+                qkv.scalar_type() == at::kFloat,
+                "attention: qkv must be bf16 or fp32, got ",
+                qkv.scalar_type());
+    TORCH_CHECK(qkv.dim() >= 3,
+                "attention: qkv must be [..., T, 3 * C] with rank >= 3, got ",
+                qkv.dim(), "-D");
+    TORCH_CHECK(qkv.is_contiguous(), "attention: qkv must be contiguous");
+    TORCH_CHECK((uintptr_t)qkv.data_ptr() % 16 == 0,
+                "attention: qkv must be 16-byte aligned");
+    const int64_t C3 = qkv.size(-1), T = qkv.size(-2);
+    TORCH_CHECK(heads >= 1 && C3 > 0 && C3 % (3 * heads) == 0,
+                "attention: the last dim must be 3 * heads * D, got ", C3,
+                " for heads = ", heads);
+    TORCH_CHECK(C3 / (3 * heads) == 64,
+                "attention: needs D == 64 (head dim), got D = ",
+                C3 / (3 * heads));
+    TORCH_CHECK(T >= 1, "attention: needs T >= 1, got T = ", T);
+    TORCH_CHECK(qkv.numel() < (1LL << 31),
+                "attention: qkv has 2^31 or more elements");
+    auto shape = qkv.sizes().vec();
+    shape.back() = C3 / 3;
+    auto out = at::empty(shape, qkv.options());
+    if (out.numel() == 0) return out;
+    defer_hip::launch_attention(bptr(qkv), bptr_mut(out),
+                                (int)(qkv.numel() / (T * C3)), (int)T,
+                                (int)heads,
+                                qkv.scalar_type() == at::kFloat,
+                                cur_stream());
+    return out;
+}
+
+// The bf16 attention kernel's work split for T tokens. Needs no GPU.
+py::dict attention_plan(int64_t T) {
+    using namespace pybind11::literals;
+    TORCH_CHECK(T >= 1 && T < (1LL << 31), "attention: needs T >= 1");
+    const auto a = defer_hip::attention_geom((int)T);
+    return py::dict("groups"_a = a.G, "groups_per_wave"_a = a.NQ,
+                    "blocks"_a = a.nblk, "groups_per_block"_a = a.gpb,
+                    "lds_bytes"_a = a.lds_bytes);
+}
+
+// y[n, 0, 0] = cls + pos[0], y[n, 0, 1 + t] = x[n, t] + pos[1 + t]: x NHWC,
+// cls fp32 [C], pos [1 + H*W, C] in x's dtype, y [N, 1, 1 + H*W, C].
+Tensor embed_tokens(Tensor x, Tensor cls, Tensor pos) {
+    TORCH_CHECK(x.dim() == 4, "embed_tokens: x must be NHWC");
+    const bool f32 = check_channel_vec(x, "embed_tokens");
+    const int64_t N = x.size(0), HW = x.size(1) * x.size(2), C = x.size(3);
+    const float* cl = channel_vec_param(cls, "embed_tokens", "cls", C);
+    TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == x.scalar_type() &&
+                pos.is_contiguous() && (uintptr_t)pos.data_ptr() % 16 == 0 &&
+                pos.dim() == 2 && pos.size(0) == HW + 1 && pos.size(1) == C,
+                "embed_tokens: pos must be a contiguous GPU [1 + H*W, C] of "
+                "x's dtype (mixed dtypes) with 1 + H*W = ", HW + 1,
+                " and C = ", C);
+    auto out = at::empty({N, 1, HW + 1, C}, x.options());
+    if (out.numel() == 0) return out;
+    if (f32)
+        defer_hip::launch_embed_tokens_f32(f32ptr(x), cl, f32ptr(pos),
+                                           out.data_ptr<float>(), N, HW,
+                                           (int)C, cur_stream());
+    else
+        defer_hip::launch_embed_tokens(bptr(x), cl, bptr(pos), bptr_mut(out),
+                                       N, HW, (int)C, cur_stream());
+    return out;
+}
+
+// [N, 1, T, C] -> [N, C], token 0 of every image: one strided device copy
+// (a memcpy node when a hipGraph is being captured), no compute kernel.
+Tensor class_token(Tensor x) {
+    TORCH_CHECK(x.is_cuda(), "class_token: x must be on GPU");
+    is_f32(x, "class_token: x");
+    TORCH_CHECK(x.dim() == 4 && x.size(1) == 1 && x.size(2) >= 1,
+                "class_token: x must be [N, 1, T, C] with T >= 1");
+    TORCH_CHECK(x.is_contiguous(), "class_token: x must be contiguous");
+    const int64_t N = x.size(0), T = x.size(2), C = x.size(3);
+    auto out = at::empty({N, C}, x.options());
+    if (out.numel() == 0) return out;
+    const size_t row = (size_t)C * x.element_size();
+    hipMemcpy2DAsync(bptr_mut(out), row, bptr(x), (size_t)T * row, row,
+                     (size_t)N, hipMemcpyDeviceToDevice, cur_stream());
+    return out;
+}
+
 // gelu(x[M, K] @ w[N, K]^T + bias): linear with the GELU epilogue. bf16: the
 // GEMM-mode plan of linear, run on its ACT_GELU instantiation; fp32: the
 // runtime act of conv_f32_kernel. The shape rules are linear's.
@@ -1741,6 +1829,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         const auto pl = defer_hip::layernorm_plan((int)C, f32 ? 4 : 8);
         return std::make_pair(pl.G, pl.VPL);
     }, py::arg("C"), py::arg("f32") = false);
+    m.def("attention", &attention, py::arg("qkv"), py::arg("heads"));
+    m.def("attention_plan", &attention_plan, py::arg("T"));
+    m.def("embed_tokens", &embed_tokens, py::arg("x"), py::arg("cls"),
+          py::arg("pos"));
+    m.def("class_token", &class_token);
     m.def("linear_gelu", &linear_gelu, py::arg("x"), py::arg("w"),
           py::arg("bias"));
     m.def("conv_ws_stats", &conv_ws_stats);

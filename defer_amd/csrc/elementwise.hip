@@ -135,6 +135,45 @@ __global__ void cat2_kernel(const bf16* __restrict__ a,
     }
 }
 
+// Token embedding of a ViT: y[n][0] = cls + pos[0], y[n][1 + t] = x[n][t] +
+// pos[1 + t]; x [N][HW][C], pos [1 + HW][C], y [N][1 + HW][C], cls fp32[C].
+// One bf16x8 chunk per thread, fp32 sums, one rounding. (A new kernel:
+// compiled without packed fp32 instructions, like the newer files.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push( \
+    __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+__global__ void embed_tokens_kernel(const bf16* __restrict__ x,
+                                    const float* __restrict__ cls,
+                                    const bf16* __restrict__ pos,
+                                    bf16* __restrict__ y, long N, long HW,
+                                    int c8n) {
+    const long T = HW + 1;
+    const long total = N * T * c8n;
+    long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    long gstride = (long)gridDim.x * blockDim.x;
+    for (long i = i0; i < total; i += gstride) {
+        const int c = (int)(i % c8n) * 8;
+        const long row = i / c8n;
+        const long t = row % T, n = row / T;
+        const bf16x8 pv = load_bf16x8(pos + (t * c8n) * 8 + c);
+        bf16x8 o;
+        if (t == 0) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = f2bf(cls[c + j] + bf2f(pv[j]));
+        } else {
+            const bf16x8 xv =
+                load_bf16x8(x + ((n * HW + t - 1) * c8n) * 8 + c);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = f2bf(bf2f(xv[j]) + bf2f(pv[j]));
+        }
+        store_bf16x8(y + i * 8, o);
+    }
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif
+
 namespace defer_hip {
 
 static int grid1d(long work, int block) {
@@ -185,6 +224,14 @@ void launch_softmax(const void* x, void* y, int rows, int cols,
     int blocks = (rows + wpb - 1) / wpb;
     hipLaunchKernelGGL(softmax_kernel, dim3(blocks), dim3(wpb * 64), 0, s,
                        (const bf16*)x, (bf16*)y, rows, cols);
+}
+
+void launch_embed_tokens(const void* x, const float* cls, const void* pos,
+                         void* y, long N, long HW, int C, hipStream_t s) {
+    const long total = N * (HW + 1) * (C / 8);
+    hipLaunchKernelGGL(embed_tokens_kernel, dim3(grid1d(total, 256)),
+                       dim3(256), 0, s, (const bf16*)x, cls, (const bf16*)pos,
+                       (bf16*)y, N, HW, C / 8);
 }
 
 }  // namespace defer_hip

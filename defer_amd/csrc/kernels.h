@@ -219,6 +219,26 @@ void launch_layernorm(const void* x, const float* weight, const float* bias,
                       void* y, long rows, int C, float eps, bool f32,
                       int max_blocks, hipStream_t s);
 
+// fused multi-head attention (attention.hip): qkv [N][T][3][heads][64], out
+// [N][T][heads][64], both in the compute dtype (f32 ? float : bf16); T >= 1,
+// qkv has fewer than 2^31 elements. attention_geom is the bf16 kernel's work
+// split, a pure function of T: G groups of 16 query rows, NQ groups per wave,
+// nblk workgroups per (image, head) of gpb groups each.
+struct AttnGeom { int G, NQ, nblk, gpb, lds_bytes; };
+AttnGeom attention_geom(int T);
+void launch_attention(const void* qkv, void* out, int N, int T, int heads,
+                      bool f32, hipStream_t s);
+
+// y[n][0][:] = cls + pos[0], y[n][1 + t][:] = x[n][t][:] + pos[1 + t]
+// (elementwise.hip / ops_f32.hip): x [N][HW][C], pos [1 + HW][C] and y
+// [N][1 + HW][C] in the compute dtype, cls fp32[C]; C % 8 == 0 (bf16) or
+// C % 4 == 0 (fp32). fp32 sums, one rounding.
+void launch_embed_tokens(const void* x, const float* cls, const void* pos,
+                         void* y, long N, long HW, int C, hipStream_t s);
+void launch_embed_tokens_f32(const float* x, const float* cls,
+                             const float* pos, float* y, long N, long HW,
+                             int C, hipStream_t s);
+
 // grouped 3x3 conv + folded BN + activation (gconv.hip), NHWC x and
 // [C][3][3][Cg] w, Cin == Cout == C, C % 16 == 0, C % Cg == 0, Cg in {4, 8,
 // 16, 32}, stride in {1, 2}, pad in {0, 1}; scale and bias non-null fp32[C];

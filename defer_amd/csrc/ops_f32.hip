@@ -187,6 +187,40 @@ __global__ void gap_f32_kernel(const float* __restrict__ x,
     st4(y + (long)n * C + c, acc);
 }
 
+// Token embedding of a ViT, fp32: y[n][0] = cls + pos[0], y[n][1 + t] =
+// x[n][t] + pos[1 + t]; one float4 per thread. (A new kernel: compiled
+// without packed fp32 instructions, like the newer files.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push( \
+    __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+__global__ void embed_tokens_f32_kernel(const float* __restrict__ x,
+                                        const float* __restrict__ cls,
+                                        const float* __restrict__ pos,
+                                        float* __restrict__ y, long N,
+                                        long HW, int c4n) {
+    const long T = HW + 1;
+    const long total = N * T * c4n;
+    long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    long gstride = (long)gridDim.x * blockDim.x;
+    for (long i = i0; i < total; i += gstride) {
+        const int c = (int)(i % c4n) * 4;
+        const long row = i / c4n;
+        const long t = row % T, n = row / T;
+        const f32x4 pv = *reinterpret_cast<const f32x4*>(
+            pos + (t * c4n) * 4 + c);
+        const f32x4 a = *reinterpret_cast<const f32x4*>(
+            t == 0 ? cls + c : x + ((n * HW + t - 1) * c4n) * 4 + c);
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = a[j] + pv[j];
+        *reinterpret_cast<f32x4*>(y + i * 4) = o;
+    }
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif
+
 int grid1d(long work, int block) {
     long g = (work + block - 1) / block;
     return (int)(g < 2048 ? g : 2048);
@@ -265,6 +299,14 @@ void launch_gap_f32(const float* x, float* y, int NB, int HW, int C,
     int cblk = (C + 1023) / 1024;
     hipLaunchKernelGGL(gap_f32_kernel, dim3(NB * cblk), dim3(256), 0, s, x,
                        y, NB, HW, C);
+}
+
+void launch_embed_tokens_f32(const float* x, const float* cls,
+                             const float* pos, float* y, long N, long HW,
+                             int C, hipStream_t s) {
+    const long total = N * (HW + 1) * (C / 4);
+    hipLaunchKernelGGL(embed_tokens_f32_kernel, dim3(grid1d(total, 256)),
+                       dim3(256), 0, s, x, cls, pos, y, N, HW, C / 4);
 }
 
 }  // namespace defer_hip

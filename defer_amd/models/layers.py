@@ -155,6 +155,48 @@ class PointwiseGelu(nn.Module):
         return 2 * self.cin * self.cout
 
 
+class Attention(nn.Module):
+    """Multi-head self-attention on a fused qkv [N, 1, T, 3 * C] (the output
+    of the block's qkv 1x1 conv), without parameters: ops.attention;
+    csrc/attention.hip on the GPU. The head dim is 64."""
+
+    def __init__(self, heads):
+        super().__init__()
+        self.heads = heads
+
+    def forward(self, qkv):
+        return ops.attention(qkv, self.heads)
+
+    def extra_repr(self):
+        return f"heads={self.heads} d={ops.ATTENTION_D}"
+
+
+class TokenEmbed(nn.Module):
+    """Patch features NHWC -> the token sequence [N, 1, 1 + H*W, C] of a
+    ViT: a class token in front, plus the position embedding
+    (ops.embed_tokens). cls_token is 1-D and stays fp32; pos_embed is 2-D,
+    so StageExecutor casts it to the compute dtype."""
+
+    def __init__(self, tokens, c):
+        super().__init__()
+        self.tokens, self.c = tokens, c
+        self.cls_token = nn.Parameter(torch.zeros(c))
+        self.pos_embed = nn.Parameter(torch.randn(tokens, c) * 0.02)
+
+    def forward(self, x):
+        return ops.embed_tokens(x, self.cls_token, self.pos_embed.to(x.dtype))
+
+    def extra_repr(self):
+        return f"tokens={self.tokens} c={self.c}"
+
+
+class ClassToken(nn.Module):
+    """[N, 1, T, C] -> [N, C]: the class token, for the head."""
+
+    def forward(self, x):
+        return ops.class_token(x)
+
+
 class GroupedConvBNAct(nn.Module):
     """Grouped 3x3 Conv2d (`groups` groups of c // groups channels, in ==
     out == c) + folded inference BatchNorm + optional activation, fused:

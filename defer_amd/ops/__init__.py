@@ -264,6 +264,107 @@ def linear_gelu(x, w, bias=None):
     return y.reshape(*x.shape[:-1], w.shape[0])
 
 
+ATTENTION_D = 64
+
+
+def attention(qkv, heads):
+    """Multi-head attention on a fused qkv: qkv is a contiguous
+    [..., T, 3 * C] of rank >= 3, bf16 or fp32, C = heads * D, with the last
+    dim laid out [3][heads][D] (q of all heads, then k, then v: what one
+    fused QKV linear produces); the leading dims are flattened to N. The
+    result is [..., T, C] in qkv's dtype:
+
+        out[n, t, h*D + d] = sum_j P[n, h, t, j] * v[n, j, h, d]
+        P[n, h, t, :]      = softmax_j((q[n, t, h, :] . k[n, j, h, :]) * D^-0.5)
+
+    Non-causal, no mask, no dropout. D == 64, T >= 1 and fewer than 2^31
+    elements, anything else raises, on the CPU too; N == 0 gives an empty
+    tensor. On the GPU one HIP kernel (csrc/attention.hip) reads q, k and v
+    in place and never writes the scores. Numerics: S is accumulated in
+    fp32; the scale 0.125 is exact; the softmax runs in fp32 with a running
+    max over key tiles of 64; the row sum l sums the fp32 p; in bf16, P is
+    rounded to bf16 (nearest even) only as the operand of the second MFMA; O
+    is accumulated in fp32 and divided by l once; one rounding to the output
+    dtype. No atomics and a fixed order of key tiles: run-to-run
+    identical. The CPU branch (ops/reference.py) keeps P in fp32."""
+    if qkv.dtype not in _VEC_DTYPES:
+        raise RuntimeError(
+            f"attention: qkv must be bf16 or fp32, got {qkv.dtype}")
+    if qkv.dim() < 3:
+        raise RuntimeError(
+            f"attention: qkv must be [..., T, 3 * C] with rank >= 3, got "
+            f"{qkv.dim()}-D")
+    if not qkv.is_contiguous():
+        raise RuntimeError("attention: qkv must be contiguous")
+    t, c3 = qkv.shape[-2], qkv.shape[-1]
+    if heads < 1 or c3 == 0 or c3 % (3 * heads):
+        raise RuntimeError(
+            f"attention: the last dim must be 3 * heads * D, got {c3} for "
+            f"heads = {heads}")
+    if c3 // (3 * heads) != ATTENTION_D:
+        raise RuntimeError(
+            f"attention: needs D == {ATTENTION_D} (head dim), got D = "
+            f"{c3 // (3 * heads)}")
+    if t < 1:
+        raise RuntimeError(f"attention: needs T >= 1, got T = {t}")
+    if qkv.numel() >= 2 ** 31:
+        raise RuntimeError("attention: qkv has 2^31 or more elements")
+    m = _backend(qkv)
+    if m is None:
+        return _ref.attention(qkv, heads)
+    return m.attention(qkv, heads)
+
+
+def attention_plan(t):
+    """The bf16 attention kernel's work split for t tokens, a pure function
+    of t: {"groups": 16-row query groups, "groups_per_wave", "blocks":
+    workgroups per (image, head), "groups_per_block", "lds_bytes"}. Needs
+    the built extension but no GPU."""
+    return dict(_built().attention_plan(t))
+
+
+def embed_tokens(x, cls, pos):
+    """NHWC x [N, H, W, C] -> tokens [N, 1, 1 + H*W, C] with a class token:
+
+        y[n, 0, 0, :]     = cls + pos[0]
+        y[n, 0, 1 + t, :] = x[n, t, :] + pos[1 + t]      (t over H*W)
+
+    cls is fp32 [C], pos [1 + H*W, C] in x's dtype. fp32 sums, one rounding.
+    On the GPU one 16-byte-vector HIP kernel; C % 8 == 0 (bf16) or
+    C % 4 == 0 (fp32), anything else raises, on the CPU too."""
+    if x.dim() != 4:
+        raise RuntimeError(
+            f"embed_tokens: x must be NHWC (4-D), got {x.dim()}-D")
+    _check_channel_vec("embed_tokens", x, (("cls", cls),))
+    want = (1 + x.shape[1] * x.shape[2], x.shape[3])
+    if (pos.dtype != x.dtype or pos.device != x.device
+            or not pos.is_contiguous() or tuple(pos.shape) != want):
+        raise RuntimeError(
+            f"embed_tokens: pos must be a contiguous {x.dtype} "
+            f"[1 + H*W, C] = {list(want)} on x's device (mixed dtypes), got "
+            f"{pos.dtype} {tuple(pos.shape)}")
+    m = _backend(x)
+    if m is None:
+        return _ref.embed_tokens(x, cls, pos)
+    return m.embed_tokens(x, cls, pos)
+
+
+def class_token(x):
+    """[N, 1, T, C] -> [N, C]: token 0 of every image. On the GPU one strided
+    device copy, as in concat_channels (no compute kernel; a memcpy node
+    under hipGraph capture)."""
+    if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] < 1:
+        raise RuntimeError(
+            f"class_token: x must be [N, 1, T, C] with T >= 1, got "
+            f"{tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise RuntimeError("class_token: x must be contiguous")
+    m = _backend(x)
+    if m is None:
+        return _ref.class_token(x)
+    return m.class_token(x)
+
+
 _GCONV_CG = (4, 8, 16, 32)
 
 

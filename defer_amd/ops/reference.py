@@ -153,6 +153,35 @@ def linear_gelu(x, w, bias=None):
     return _gelu_f32(y).to(x.dtype)
 
 
+def attention(qkv, heads):
+    """Multi-head attention on a fused qkv [..., T, 3 * C] whose last dim is
+    laid out [3][heads][D]: out[..., t, h*D + d] = sum_j P[h, t, j] *
+    v[j, h, d] with P = softmax_j(q . k * D^-0.5). All of it in fp32, P
+    included, one rounding to qkv's dtype."""
+    t, c3 = qkv.shape[-2], qkv.shape[-1]
+    d = c3 // (3 * heads)
+    q, k, v = (qkv.float().reshape(-1, t, 3, heads, d)
+               .permute(2, 0, 3, 1, 4))                 # each [N, heads, T, D]
+    p = torch.softmax(q @ k.transpose(-1, -2) * d ** -0.5, dim=-1)
+    out = (p @ v).permute(0, 2, 1, 3).reshape(*qkv.shape[:-1], c3 // 3)
+    return out.to(qkv.dtype)
+
+
+def embed_tokens(x, cls, pos):
+    """NHWC x -> tokens [N, 1, 1 + H*W, C]: the class token cls (fp32 [C])
+    in front of the H*W patch tokens, plus pos [1 + H*W, C]; fp32 sums, one
+    rounding."""
+    n, c = x.shape[0], x.shape[-1]
+    tok = torch.cat([cls.float().expand(n, 1, c),
+                     x.float().reshape(n, -1, c)], dim=1) + pos.float()
+    return tok.unsqueeze(1).to(x.dtype)
+
+
+def class_token(x):
+    """[N, 1, T, C] -> [N, C]: token 0 of every image."""
+    return x[:, 0, 0, :].contiguous()
+
+
 def batchnorm_apply(x, scale, bias, act="none"):
     """Standalone inference batchnorm (y = x*scale + bias), NHWC.
 

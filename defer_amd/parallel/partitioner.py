@@ -147,6 +147,14 @@ def node_times(graph: LayerGraph, input_shape=(1, 224, 224, 3),
             # a GEMM-mode 1x1 conv with another epilogue
             f = float(torch.tensor(out[:-1]).prod()) * lay.flops_per_pixel()
             t = max(f / _EFF_1X1, (in_b + out_b) / _BW_STREAM)
+        elif isinstance(lay, L.Attention):
+            # csrc/attention.hip: Q K^T and P V, 2 * T * T * D flops each per
+            # head; qkv is read once and the output written once, the scores
+            # stay on the CU. The MFMA work is costed at the 1x1 class's rate.
+            tok = float(out[-2])
+            f = (4.0 * tok * tok * 64 * lay.heads
+                 * float(torch.tensor(out[:-2]).prod()))
+            t = max(f / _EFF_1X1, (in_b + out_b) / _BW_STREAM)
         elif isinstance(lay, L.GroupedConvBNAct):
             # the MFMA kernel of csrc/gconv.hip: the useful flops at the 3x3
             # rate or, far more often, one pass over input and output
