@@ -97,11 +97,18 @@ __global__ __launch_bounds__(TPB, WPS) void conv_igemm_kernel(
     const bf16* __restrict__ RES = (const bf16*)p.res;
     bf16* __restrict__ OUT = (bf16*)p.out;
 
-    // wave tiling: WMW waves along m (32 rows each), WNW along n
+    // wave tiling: WMW waves along m (WM rows each), WNW along n (WN
+    // columns each); a wave owns MI x NI 16x16 fragments. The 128x128
+    // tile's four waves sit 2 x 2 (64 x 64 a wave: 4 A + 4 B fragment
+    // reads per 16 MFMAs, where 4 x 1 needs 2 + 8); every other tile
+    // stacks 32-row slabs along m.
     constexpr int NW = TPB / WAVE;              // waves per block
-    constexpr int WMW = BM / 32;                // m-slabs of 32 rows
+    constexpr bool SQ = BM == 128 && BN == 128 && NW == 4;
+    constexpr int WMW = SQ ? 2 : BM / 32;       // waves along m
     constexpr int WNW = NW / WMW;               // waves along n
+    constexpr int WM = BM / WMW;                // wave m-height
     constexpr int WN = BN / WNW;                // wave n-width
+    constexpr int MI = WM / 16;                 // A frags per wave
     constexpr int NI = WN / 16;                 // B frags per wave
     constexpr int ACH = BM * 8 / TPB;           // A chunks per thread
     constexpr int BCH = BN * 8 / TPB;           // B chunks per thread
@@ -308,16 +315,69 @@ __global__ __launch_bounds__(TPB, WPS) void conv_igemm_kernel(
         }
     };
 
-    f32x4 acc[2][NI];
+    f32x4 acc[MI][NI];
     auto compute = [&](int abuf, int bbuf) {
         bf16* A = A0 + abuf * BM * BK;
         bf16* B = B0 + bbuf * BN * BK;
+        if constexpr (SQ) {
+            // the fragment reads of step ks + 1 are issued in front of the
+            // MFMAs of step ks and pinned by sched_barrier; never across
+            // the k-tile barrier (the next buffer has not landed before
+            // that wait). The wait for step 0 is written out: while a
+            // global_load_lds is pending hipcc turns its first LDS wait
+            // into lgkmcnt(0), which must fall before the reads of step 1
+            // are issued, not behind them. The CONV and STEM gathers and
+            // the GELU epilogue have no registers for a second A set
+            // (they spilled) and read only B ahead.
+            constexpr bool PF_A = (AMODE == AMODE_GEMM ||
+                                   AMODE == AMODE_RSC) && ACT != ACT_GELU;
+            bf16x8 af[PF_A ? BK / 32 : 1][MI], bfr[BK / 32][NI];
+            auto a_frags = [&](int set, int ks) {
+#pragma unroll
+                for (int mi = 0; mi < MI; ++mi) {
+                    int row = wm * WM + mi * 16 + lo16;
+                    af[set][mi] = *reinterpret_cast<bf16x8*>(
+                        A + row * BK + swz(row, ks * 4 + hi4) * 8);
+                }
+            };
+            auto b_frags = [&](int ks) {
+#pragma unroll
+                for (int ni = 0; ni < NI; ++ni) {
+                    int row = wn * WN + ni * 16 + lo16;
+                    bfr[ks][ni] = *reinterpret_cast<bf16x8*>(
+                        B + row * BK + swz(row, ks * 4 + hi4) * 8);
+                }
+            };
+            __builtin_amdgcn_sched_barrier(0);   // the stages issue first
+            a_frags(0, 0);
+            b_frags(0);
+            __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int ks = 0; ks < BK / 32; ++ks) {
+                if (ks + 1 < BK / 32) {
+                    if (PF_A) a_frags(ks + 1, ks + 1);
+                    b_frags(ks + 1);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+                    for (int ni = 0; ni < NI; ++ni)
+                        acc[mi][ni] = MFMA_BF16_16x16x32(
+                            af[PF_A ? ks : 0][mi], bfr[ks][ni],
+                            acc[mi][ni]);
+                __builtin_amdgcn_sched_barrier(0);
+                if (!PF_A && ks + 1 < BK / 32) a_frags(0, ks + 1);
+            }
+            return;
+        }
 #pragma unroll
         for (int ks = 0; ks < BK / 32; ++ks) {
-            bf16x8 af[2], bfr[NI];
+            bf16x8 af[MI], bfr[NI];
 #pragma unroll
-            for (int mi = 0; mi < 2; ++mi) {
-                int row = wm * 32 + mi * 16 + lo16;
+            for (int mi = 0; mi < MI; ++mi) {
+                int row = wm * WM + mi * 16 + lo16;
                 af[mi] = *reinterpret_cast<bf16x8*>(
                     A + row * BK + swz(row, ks * 4 + hi4) * 8);
             }
@@ -328,7 +388,7 @@ __global__ __launch_bounds__(TPB, WPS) void conv_igemm_kernel(
                     B + row * BK + swz(row, ks * 4 + hi4) * 8);
             }
 #pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
+            for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
                 for (int ni = 0; ni < NI; ++ni)
                     acc[mi][ni] =
@@ -349,12 +409,12 @@ __global__ __launch_bounds__(TPB, WPS) void conv_igemm_kernel(
         for (int h = 0; h < ROUNDS; ++h) {
             const int r0 = h * RH;           // tile-local first row
 #pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
+            for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
                 for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        int r = wm * 32 + mi * 16 + hi4 * 4 + e;
+                        int r = wm * WM + mi * 16 + hi4 * 4 + e;
                         if (r < r0 || r >= r0 + RH) continue;
                         int c = wn * WN + ni * 16 + lo16;
                         int rl = r - r0;
@@ -474,7 +534,7 @@ __global__ __launch_bounds__(TPB, WPS) void conv_igemm_kernel(
     int it = 0;   // computed-iteration counter; tile i -> buffer i%DA
     for (int mt = blockIdx.x; mt < mtiles; mt += gridDim.x) {
 #pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
+        for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
             for (int ni = 0; ni < NI; ++ni)
                 acc[mi][ni] = {0.f, 0.f, 0.f, 0.f};

@@ -38,6 +38,11 @@ RESNET_SHAPES = [
     ("L4.c3x3_512s2", 14, 14, 512, 512, 3, 2, 1, False),
     ("L4.c3x3_512", 7, 7, 512, 512, 3, 1, 1, False),
     ("L4.c1x1_2048+res", 7, 7, 512, 2048, 1, 1, 0, True),
+    # the other rows of the 128x128 tile at batch 256: layer4 conv1 of
+    # blocks 2-3 and the stride-2 projections of layers 3 and 4
+    ("L4.c1x1_512from2048", 7, 7, 2048, 512, 1, 1, 0, False),
+    ("L3.proj1024s2", 28, 28, 512, 1024, 1, 2, 0, False),
+    ("L4.proj2048s2", 14, 14, 1024, 2048, 1, 2, 0, False),
 ]
 
 VGG_SHAPES = [
@@ -93,17 +98,28 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--only", default="",
+                    help="comma-separated shape names; default all")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed windows per shape; prints min..max us")
     args = ap.parse_args()
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     shapes = RESNET_SHAPES if args.model == "resnet50" else VGG_SHAPES
+    if args.only:
+        only = args.only.split(",")
+        shapes = [s for s in shapes if s[0] in only]
+        assert len(shapes) == len(only), f"unknown shape in {only}"
     total = 0.0
     rows = []
     for s in shapes:
-        r = bench_shape(*s, args.batch, args.iters, dtype, args.warmup)
+        reps = [bench_shape(*s, args.batch, args.iters, dtype, args.warmup)
+                for _ in range(args.repeats)]
+        r = min(reps, key=lambda q: q["us"])
+        r["us_max"] = max(q["us"] for q in reps)
         rows.append(r)
         print(f"{r['name']:22s} M={r['M']:7d} N={r['N']:4d} K={r['K']:5d} "
-              f"{r['us']:8.1f} us  {r['tflops']:7.1f} TF  "
-              f">={r['min_gbps']:6.0f} GB/s")
+              f"{r['us']:8.1f}..{r['us_max']:.1f} us  "
+              f"{r['tflops']:7.1f} TF  >={r['min_gbps']:6.0f} GB/s")
         total += r["us"]
     print(f"total (one call each): {total:.1f} us")
     print(json.dumps(rows))

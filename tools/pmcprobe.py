@@ -20,6 +20,8 @@ SHAPES = {
     "l1c1": (64, 56, 56, 64, 64, 1, 1, 0, False),
     # layer1 3x3 at the bench batch (DEFER_CONV_WS=0 for the older kernel)
     "l1c2": (256, 56, 56, 64, 64, 3, 1, 1, False),
+    # layer2 3x3 at the bench batch: the 128x128 implicit-GEMM tile
+    "l2c2": (256, 28, 28, 128, 128, 3, 1, 1, False),
 }
 
 
