@@ -170,6 +170,32 @@ __global__ void embed_tokens_kernel(const bf16* __restrict__ x,
         store_bf16x8(y + i * 8, o);
     }
 }
+
+// Patch merging gather of a Swin stage: y[n][oh][ow][k][:] = x[n][2*oh +
+// (k & 1)][2*ow + (k >> 1)][:] for k < 4 (torchvision's order of the four
+// pixels); x [N][H][W][C], y [N][H/2][W/2][4C]. One bf16x8 chunk per thread
+// and turn, linear in y: a copy, bit for bit.
+__global__ void patch_merge_kernel(const bf16* __restrict__ x,
+                                   bf16* __restrict__ y, long N, int H, int W,
+                                   int c8n) {
+    const int OH = H / 2, OW = W / 2;
+    const long total = N * OH * OW * 4 * c8n;
+    long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    long gstride = (long)gridDim.x * blockDim.x;
+    for (long i = i0; i < total; i += gstride) {
+        const int c = (int)(i % c8n);
+        long r = i / c8n;
+        const int k = (int)(r & 3);
+        r >>= 2;
+        const int ow = (int)(r % OW);
+        r /= OW;
+        const int oh = (int)(r % OH);
+        const long n = r / OH;
+        const long src = ((n * H + 2 * oh + (k & 1)) * W + 2 * ow + (k >> 1)) *
+                             c8n + c;
+        store_bf16x8(y + i * 8, load_bf16x8(x + src * 8));
+    }
+}
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute pop
 #endif
@@ -232,6 +258,14 @@ void launch_embed_tokens(const void* x, const float* cls, const void* pos,
     hipLaunchKernelGGL(embed_tokens_kernel, dim3(grid1d(total, 256)),
                        dim3(256), 0, s, (const bf16*)x, cls, (const bf16*)pos,
                        (bf16*)y, N, HW, C / 8);
+}
+
+void launch_patch_merge(const void* x, void* y, long N, int H, int W, int C,
+                        hipStream_t s) {
+    const long total = N * H * W * (C / 8);
+    hipLaunchKernelGGL(patch_merge_kernel, dim3(grid1d(total, 256)),
+                       dim3(256), 0, s, (const bf16*)x, (bf16*)y, N, H, W,
+                       C / 8);
 }
 
 }  // namespace defer_hip

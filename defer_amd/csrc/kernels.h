@@ -229,6 +229,31 @@ AttnGeom attention_geom(int T);
 void launch_attention(const void* qkv, void* out, int N, int T, int heads,
                       bool f32, hipStream_t s);
 
+// shifted-window attention (window_attention.hip): qkv [N][H][W][3][heads][32],
+// out [N][H][W][heads][32] and table [(2w - 1)^2][heads], all in the compute
+// dtype (f32 ? float : bf16); 2 <= w, w * w <= 64, w divides H and W,
+// 0 <= shift < w, qkv has fewer than 2^31 elements. window_attention_geom is
+// the bf16 kernel's work split, a pure function of the shape: T = w * w tokens
+// in `groups` 16-row query groups, `windows` per image, one wave per (image,
+// window, head) pair, four pairs per workgroup, `idle_waves` in the last one.
+struct WinAttnGeom {
+    int T, groups, windows;
+    long pairs, blocks;
+    int idle_waves, lds_bytes;
+};
+WinAttnGeom window_attention_geom(int N, int H, int W, int heads, int w);
+void launch_window_attention(const void* qkv, const void* table, void* out,
+                             int N, int H, int W, int heads, int w, int shift,
+                             bool f32, hipStream_t s);
+
+// y[n][oh][ow][k*C + c] = x[n][2*oh + (k & 1)][2*ow + (k >> 1)][c], k < 4
+// (elementwise.hip / ops_f32.hip): Swin's patch merging gather, a pure copy
+// in 16-byte vectors; H and W even, C % 8 == 0 (bf16) or C % 4 == 0 (fp32).
+void launch_patch_merge(const void* x, void* y, long N, int H, int W, int C,
+                        hipStream_t s);
+void launch_patch_merge_f32(const float* x, float* y, long N, int H, int W,
+                            int C, hipStream_t s);
+
 // y[n][0][:] = cls + pos[0], y[n][1 + t][:] = x[n][t][:] + pos[1 + t]
 // (elementwise.hip / ops_f32.hip): x [N][HW][C], pos [1 + HW][C] and y
 // [N][1 + HW][C] in the compute dtype, cls fp32[C]; C % 8 == 0 (bf16) or

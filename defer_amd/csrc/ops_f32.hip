@@ -217,6 +217,32 @@ __global__ void embed_tokens_f32_kernel(const float* __restrict__ x,
         *reinterpret_cast<f32x4*>(y + i * 4) = o;
     }
 }
+
+// Patch merging gather of a Swin stage, fp32: y[n][oh][ow][k][:] = x[n][2*oh
+// + (k & 1)][2*ow + (k >> 1)][:] for k < 4; one float4 per thread and turn,
+// linear in y: a copy, bit for bit.
+__global__ void patch_merge_f32_kernel(const float* __restrict__ x,
+                                       float* __restrict__ y, long N, int H,
+                                       int W, int c4n) {
+    const int OH = H / 2, OW = W / 2;
+    const long total = N * OH * OW * 4 * c4n;
+    long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    long gstride = (long)gridDim.x * blockDim.x;
+    for (long i = i0; i < total; i += gstride) {
+        const int c = (int)(i % c4n);
+        long r = i / c4n;
+        const int k = (int)(r & 3);
+        r >>= 2;
+        const int ow = (int)(r % OW);
+        r /= OW;
+        const int oh = (int)(r % OH);
+        const long n = r / OH;
+        const long src = ((n * H + 2 * oh + (k & 1)) * W + 2 * ow + (k >> 1)) *
+                             c4n + c;
+        *reinterpret_cast<f32x4*>(y + i * 4) =
+            *reinterpret_cast<const f32x4*>(x + src * 4);
+    }
+}
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute pop
 #endif
@@ -307,6 +333,13 @@ void launch_embed_tokens_f32(const float* x, const float* cls,
     const long total = N * (HW + 1) * (C / 4);
     hipLaunchKernelGGL(embed_tokens_f32_kernel, dim3(grid1d(total, 256)),
                        dim3(256), 0, s, x, cls, pos, y, N, HW, C / 4);
+}
+
+void launch_patch_merge_f32(const float* x, float* y, long N, int H, int W,
+                            int C, hipStream_t s) {
+    const long total = N * H * W * (C / 4);
+    hipLaunchKernelGGL(patch_merge_f32_kernel, dim3(grid1d(total, 256)),
+                       dim3(256), 0, s, x, y, N, H, W, C / 4);
 }
 
 }  // namespace defer_hip

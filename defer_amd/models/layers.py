@@ -34,7 +34,7 @@ class ConvBNAct(nn.Module):
     """
 
     def __init__(self, cin, cout, kernel=3, stride=1, padding=None,
-                 act="relu", bn=True):
+                 act="relu", bn=True, bias=True):
         super().__init__()
         self.cin, self.cout = cin, cout
         self.kernel, self.stride = kernel, stride
@@ -44,7 +44,7 @@ class ConvBNAct(nn.Module):
         w = torch.randn(cout, kernel, kernel, cin) * math.sqrt(2.0 / fan_in)
         self.weight = nn.Parameter(w)
         self.scale = nn.Parameter(torch.ones(cout)) if bn else None
-        self.bias = nn.Parameter(torch.zeros(cout))
+        self.bias = nn.Parameter(torch.zeros(cout)) if bias else None
 
     def forward(self, x, residual=None):
         return ops.conv2d_bn_act(
@@ -169,6 +169,39 @@ class Attention(nn.Module):
 
     def extra_repr(self):
         return f"heads={self.heads} d={ops.ATTENTION_D}"
+
+
+class WindowAttention(nn.Module):
+    """Swin's (shifted-)window multi-head self-attention on a fused NHWC qkv
+    [N, H, W, 3 * C], the output of the block's qkv 1x1 conv:
+    ops.window_attention; csrc/window_attention.hip on the GPU. The head dim
+    is 32. relative_position_bias_table is [(2 * window - 1)**2, heads], 2-D,
+    so StageExecutor casts it to the compute dtype."""
+
+    def __init__(self, heads, window, shift=0):
+        super().__init__()
+        if not 0 <= shift < window:
+            raise ValueError(f"shift={shift} is outside [0, window={window})")
+        self.heads, self.window, self.shift = heads, window, shift
+        self.relative_position_bias_table = nn.Parameter(
+            torch.randn((2 * window - 1) ** 2, heads) * 0.02)
+
+    def forward(self, qkv):
+        return ops.window_attention(
+            qkv, self.relative_position_bias_table.to(qkv.dtype), self.heads,
+            self.window, self.shift)
+
+    def extra_repr(self):
+        return (f"heads={self.heads} d={ops.WINDOW_ATTENTION_D} "
+                f"window={self.window} shift={self.shift}")
+
+
+class PatchMerge(nn.Module):
+    """[N, H, W, C] -> [N, H/2, W/2, 4C]: the gather of Swin's patch merging
+    (ops.patch_merge), before its LayerNormC(4C) and bias-free linear."""
+
+    def forward(self, x):
+        return ops.patch_merge(x)
 
 
 class TokenEmbed(nn.Module):

@@ -323,6 +323,116 @@ def attention_plan(t):
     return dict(_built().attention_plan(t))
 
 
+WINDOW_ATTENTION_D = 32
+
+
+def window_attention(qkv, bias_table, heads, window, shift=0):
+    """Swin's shifted-window attention on a fused NHWC qkv: qkv is a
+    contiguous [N, H, W, 3 * C], bf16 or fp32, C = heads * 32, with the last
+    dim laid out [3][heads][32] (what the block's qkv 1x1 conv writes);
+    bias_table is the learned relative-position bias, a contiguous
+    [(2 * window - 1)**2, heads] in qkv's dtype. The result is [N, H, W, C]
+    in qkv's dtype. With w = window, s = shift, T = w * w:
+
+        shifted frame: (r', c') holds pixel ((r' + s) % H, (c' + s) % W),
+            i.e. torch.roll(x, (-s, -s), (1, 2))
+        window (r' // w, c' // w), token t = (r' % w) * w + (c' % w) = (i, j)
+        score(tq, tk) = (q . k) * 32**-0.5
+            + bias_table[(iq - ik + w - 1) * (2w - 1) + (jq - jk + w - 1), head]
+            + mask
+        mask = -100 (added, not an exclusion) when s > 0 and the tokens' row
+            regions or column regions differ; the region of a shifted row r'
+            is 0 for r' < H - w, 1 for r' < H - s, else 2; columns with W
+        out[pixel of tq] = sum_tk softmax_tk(score)[tk] * v[pixel of tk]
+
+    These are the semantics of the original implementation and of
+    torchvision. On the GPU one HIP kernel (csrc/window_attention.hip) does
+    the roll, the partition, the bias gather, the mask and their inverses in
+    its addressing: nothing but qkv is read and nothing but the result
+    written, with no host sync. Scores, bias, softmax and normalisation are
+    fp32; in bf16, P is rounded to bf16 once as the operand of the second
+    MFMA; one rounding of the output; run-to-run identical. dtype, a 4-D
+    contiguous qkv, last dim 3 * heads * 32, 2 <= window with window**2 <=
+    64, window dividing H and W, 0 <= shift < window, the table's shape and
+    dtype, and fewer than 2^31 elements: anything else raises, on the CPU
+    too. N == 0 gives an empty tensor. The CPU branch (ops/reference.py)
+    keeps P in fp32."""
+    if qkv.dtype not in _VEC_DTYPES:
+        raise RuntimeError(
+            f"window_attention: qkv must be bf16 or fp32, got {qkv.dtype}")
+    if qkv.dim() != 4:
+        raise RuntimeError(
+            f"window_attention: qkv must be NHWC (4-D), got {qkv.dim()}-D")
+    if not qkv.is_contiguous():
+        raise RuntimeError("window_attention: qkv must be contiguous")
+    h, w, c3 = qkv.shape[1:]
+    if heads < 1 or c3 != 3 * heads * WINDOW_ATTENTION_D:
+        raise RuntimeError(
+            f"window_attention: the last dim must be 3 * heads * "
+            f"{WINDOW_ATTENTION_D}, got {c3} for heads = {heads}")
+    if window < 2 or window * window > 64:
+        raise RuntimeError(
+            f"window_attention: needs 2 <= window and window^2 <= 64, got "
+            f"window = {window}")
+    if h == 0 or w == 0 or h % window or w % window:
+        raise RuntimeError(
+            f"window_attention: window must divide H and W, got {h}x{w} for "
+            f"window = {window}")
+    if not 0 <= shift < window:
+        raise RuntimeError(
+            f"window_attention: needs 0 <= shift < window, got shift = "
+            f"{shift}")
+    want = ((2 * window - 1) ** 2, heads)
+    if (bias_table.dtype != qkv.dtype or bias_table.device != qkv.device
+            or not bias_table.is_contiguous()
+            or tuple(bias_table.shape) != want):
+        raise RuntimeError(
+            f"window_attention: bias_table must be a contiguous {qkv.dtype} "
+            f"[(2*window - 1)^2, heads] = {list(want)} on qkv's device "
+            f"(mixed dtypes), got {bias_table.dtype} "
+            f"{tuple(bias_table.shape)}")
+    if qkv.numel() >= 2 ** 31:
+        raise RuntimeError("window_attention: qkv has 2^31 or more elements")
+    m = _backend(qkv)
+    if m is None:
+        return _ref.window_attention(qkv, bias_table, heads, window, shift)
+    return m.window_attention(qkv, bias_table, heads, window, shift)
+
+
+def window_attention_plan(n, h, w, heads, window):
+    """The bf16 window attention kernel's work split for an [n, h, w, 3 *
+    heads * 32] qkv, a pure function of the shape: {"tokens": T, "groups":
+    16-row query groups of a window, "windows": per image, "pairs": (image,
+    window, head) triples, one wave each, "blocks": workgroups of four
+    waves, "idle_waves": in the last block, "lds_bytes"}. Needs the built
+    extension but no GPU."""
+    return dict(_built().window_attention_plan(n, h, w, heads, window))
+
+
+def patch_merge(x):
+    """Swin's patch merging gather, NHWC [N, H, W, C] -> [N, H/2, W/2, 4C]:
+    the four pixels of each 2x2 patch side by side in the channels, in
+    torchvision's order (even row, even col), (odd, even), (even, odd),
+    (odd, odd):
+
+        y[n, oh, ow, k*C + c] = x[n, 2*oh + (k & 1), 2*ow + (k >> 1), c]
+
+    A copy, bit for bit; on the GPU one 16-byte-vector HIP kernel. Odd H or
+    W raises, and C % 8 == 0 (bf16) or C % 4 == 0 (fp32), on the CPU too."""
+    if x.dim() != 4:
+        raise RuntimeError(
+            f"patch_merge: x must be NHWC (4-D), got {x.dim()}-D")
+    _check_channel_vec("patch_merge", x, ())
+    if x.shape[1] % 2 or x.shape[2] % 2:
+        raise RuntimeError(
+            f"patch_merge: H and W must be even, got {x.shape[1]}x"
+            f"{x.shape[2]}")
+    m = _backend(x)
+    if m is None:
+        return _ref.patch_merge(x)
+    return m.patch_merge(x)
+
+
 def embed_tokens(x, cls, pos):
     """NHWC x [N, H, W, C] -> tokens [N, 1, 1 + H*W, C] with a class token:
 

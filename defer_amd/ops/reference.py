@@ -167,6 +167,56 @@ def attention(qkv, heads):
     return out.to(qkv.dtype)
 
 
+def _window_regions(size, window, shift):
+    """The region 0, 1 or 2 of every shifted row (or column) of a map."""
+    r = torch.arange(size)
+    return (r >= size - window).long() + (r >= size - shift).long()
+
+
+def window_attention(qkv, bias_table, heads, window, shift=0):
+    """Swin's shifted-window attention on an NHWC qkv [N, H, W, 3 * C] whose
+    last dim is [3][heads][32], as the plain composition: roll by -shift,
+    partition into windows, q k^T * 32^-0.5 plus the index-gathered
+    relative-position bias plus the -100 mask of the shifted regions,
+    softmax, P v, reverse partition, roll back. All of it in fp32, P
+    included, one rounding to qkv's dtype. This is the specification of
+    ops.window_attention."""
+    n, hh, ww, c3 = qkv.shape
+    w, s, t, c = window, shift, window * window, c3 // 3
+    d = c // heads
+    x = torch.roll(qkv.float(), (-s, -s), (1, 2))
+    x = (x.reshape(n, hh // w, w, ww // w, w, 3, heads, d)
+         .permute(5, 0, 1, 3, 6, 2, 4, 7)
+         .reshape(3, n, hh // w, ww // w, heads, t, d))
+    q, k, v = x[0], x[1], x[2]                  # [N, nh, nw, heads, T, D]
+    score = q @ k.transpose(-1, -2) * d ** -0.5
+    ij = torch.stack(torch.meshgrid(torch.arange(w), torch.arange(w),
+                                    indexing="ij")).reshape(2, t)
+    rel = ij[:, :, None] - ij[:, None, :] + w - 1           # [2, T, T]
+    index = rel[0] * (2 * w - 1) + rel[1]
+    bias = bias_table.float()[index.reshape(-1)].reshape(t, t, heads)
+    score = score + bias.permute(2, 0, 1).to(score.device)
+    if s > 0:
+        reg = (_window_regions(hh, w, s)[:, None] * 3
+               + _window_regions(ww, w, s)[None, :])        # [H, W]
+        reg = (reg.reshape(hh // w, w, ww // w, w).permute(0, 2, 1, 3)
+               .reshape(hh // w, ww // w, t))
+        apart = reg[:, :, :, None] != reg[:, :, None, :]    # [nh, nw, T, T]
+        mask = torch.zeros(apart.shape).masked_fill(apart, -100.0)
+        score = score + mask[:, :, None].to(score.device)
+    out = torch.softmax(score, dim=-1) @ v                  # [N, nh, nw, h, T, D]
+    out = (out.reshape(n, hh // w, ww // w, heads, w, w, d)
+           .permute(0, 1, 4, 2, 5, 3, 6).reshape(n, hh, ww, c))
+    return torch.roll(out, (s, s), (1, 2)).to(qkv.dtype)
+
+
+def patch_merge(x):
+    """NHWC [N, H, W, C] -> [N, H/2, W/2, 4C]: (even row, even col), (odd,
+    even), (even, odd), (odd, odd) of every 2x2 patch, torchvision's order."""
+    return torch.cat([x[:, 0::2, 0::2], x[:, 1::2, 0::2], x[:, 0::2, 1::2],
+                      x[:, 1::2, 1::2]], dim=-1).contiguous()
+
+
 def embed_tokens(x, cls, pos):
     """NHWC x -> tokens [N, 1, 1 + H*W, C]: the class token cls (fp32 [C])
     in front of the H*W patch tokens, plus pos [1 + H*W, C]; fp32 sums, one

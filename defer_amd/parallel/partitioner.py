@@ -155,6 +155,17 @@ def node_times(graph: LayerGraph, input_shape=(1, 224, 224, 3),
             f = (4.0 * tok * tok * 64 * lay.heads
                  * float(torch.tensor(out[:-2]).prod()))
             t = max(f / _EFF_1X1, (in_b + out_b) / _BW_STREAM)
+        elif isinstance(lay, L.WindowAttention):
+            # csrc/window_attention.hip: Q K^T and P V inside each window, 2 *
+            # T * T * 32 flops each per head and window; qkv is read once and
+            # the output written once. MFMA work at the 1x1 class's rate.
+            tok = float(lay.window ** 2)
+            f = (4.0 * tok * tok * 32 * lay.heads
+                 * float(out[0] * out[1] * out[2]) / tok)
+            t = max(f / _EFF_1X1, (in_b + out_b) / _BW_STREAM)
+        elif isinstance(lay, L.PatchMerge):
+            # a gather: one pass over input and output
+            t = (in_b + out_b) / _BW_ELTW
         elif isinstance(lay, L.GroupedConvBNAct):
             # the MFMA kernel of csrc/gconv.hip: the useful flops at the 3x3
             # rate or, far more often, one pass over input and output
