@@ -292,6 +292,43 @@ void launch_se_gate(const void* x, const void* w1, const float* b1,
 void launch_channel_scale(const void* x, const float* g, void* y, long NB,
                           long HW, int C, bool f32, hipStream_t s);
 
+// ---- fp8 (OCP e4m3) path (conv_fp8.hip) ----
+// out = clamp(conv(x, w) * scale[c] + bias[c] + res_scale * res, act_lo,
+// act_hi) on the fp8 MFMA with fp32 accumulation; x, w and res are e4m3
+// bytes, out e4m3 of clamp(v * out_inv_scale, +-448) (out_fp8) or bf16.
+// Cin % 16 == 0, Cout % 16 == 0, stride and pad free; scale and bias
+// non-null fp32[Cout]; every pointer 16-byte aligned. A 1x1/s1/p0 conv is
+// passed as the GEMM H = OH = 1, W = OW = M.
+struct ConvFp8Params {
+    const unsigned char* x;     // [NB, H, W, Cin] e4m3
+    const unsigned char* w;     // [Cout][K] e4m3 (OHWI flattened)
+    const float* scale;         // [Cout]
+    const float* bias;          // [Cout]
+    const unsigned char* res;   // [M][Cout] e4m3 or null
+    void* out;                  // [M][Cout] e4m3 or bf16
+    const void* zbuf;           // >= 16 B zeros
+    int M, K, Cout;
+    int H, W, Cin;
+    int OH, OW, S, stride, pad;
+    float act_lo, act_hi;       // (-inf, inf) none, (0, inf) relu, (0, 6)
+    float res_scale, out_inv_scale;
+    int out_fp8;
+    int ntm, ntn;               // filled by the launcher
+};
+// the tile policy, a pure function of the GEMM shape: bm x bn is 128x128
+// or 64x64; max_blocks caps the grid (0 = policy) so few workgroups walk
+// many tiles.
+struct ConvFp8Plan {
+    int bm, bn, ntm, ntn, ktiles, grid, lds_bytes;
+    bool narrow;            // K < 128: the bf16 MFMA on widened bytes
+};
+ConvFp8Plan plan_conv_fp8(long M, int Cout, int K, int max_blocks);
+ConvFp8Plan launch_conv_fp8(ConvFp8Params p, int max_blocks, hipStream_t s);
+// y = e4m3(clamp(x * inv_scale, -448, 448)), round to nearest even; x bf16
+// or fp32, n % 16 == 0, both 16-byte aligned.
+void launch_quantize_fp8(const void* x, void* y, long n, bool f32,
+                         float inv_scale, int max_blocks, hipStream_t s);
+
 // NCHW <-> NHWC conversion with an optional fp32 <-> bf16 conversion in the
 // same pass (layout.hip). x is [N, C, HW] when to_nhwc, [N, HW, C]
 // otherwise, and y the other one; both contiguous. fp32 -> bf16 rounds to

@@ -300,6 +300,70 @@ class SqueezeExcite(nn.Module):
         return 4 * self.c * self.cr
 
 
+class QuantizeFP8(nn.Module):
+    """bf16 / fp32 activation -> e4m3 of x / scale (ops.quantize_fp8), with
+    a static per-tensor scale from calibration (defer_amd.quant)."""
+
+    def __init__(self, scale):
+        super().__init__()
+        self.scale = float(scale)
+
+    def forward(self, x):
+        return ops.quantize_fp8(x, self.scale)
+
+    def extra_repr(self):
+        return f"scale={self.scale:.4g}"
+
+
+class ConvBNActFP8(nn.Module):
+    """Conv + folded BN + optional residual + activation on e4m3 bytes
+    (ops.conv2d_bn_act_fp8), made from a ConvBNAct by defer_amd.quant.
+
+    The e4m3 weights (per-output-channel scales amax / 448) and the fp32
+    epilogue vectors are buffers, not parameters: StageExecutor re-casts
+    parameters to the compute dtype and these must stay what they are.
+    scale[c] = bn_scale[c] * x_scale * w_scale[c]. out_scale None writes
+    bf16, otherwise e4m3 of v / out_scale. Not a ConvBNAct subclass, so the
+    bf16 fusion passes leave it alone."""
+
+    def __init__(self, conv, act, x_scale, res_scale=None, out_scale=None):
+        super().__init__()
+        self.cin, self.cout = conv.cin, conv.cout
+        self.kernel, self.stride = conv.kernel, conv.stride
+        self.padding, self.act = conv.padding, act
+        w = conv.weight.detach().float()
+        w_scale = w.abs().amax(dim=(1, 2, 3)).clamp_min(1e-12) / 448.0
+        # one-time pack on whatever device the conv lives on
+        self.register_buffer(
+            "weight_q", (w / w_scale.view(-1, 1, 1, 1)).clamp(-448.0, 448.0)
+            .to(torch.float8_e4m3fn).contiguous())
+        bn = (conv.scale.detach().float() if conv.scale is not None
+              else torch.ones(conv.cout, device=w.device))
+        self.register_buffer("scale", bn * float(x_scale) * w_scale)
+        self.register_buffer(
+            "bias", conv.bias.detach().float().clone()
+            if conv.bias is not None
+            else torch.zeros(conv.cout, device=w.device))
+        self.x_scale = float(x_scale)
+        self.res_scale = None if res_scale is None else float(res_scale)
+        self.out_scale = None if out_scale is None else float(out_scale)
+
+    def forward(self, x, residual=None):
+        return ops.conv2d_bn_act_fp8(
+            x, self.weight_q, self.scale, self.bias, stride=self.stride,
+            padding=self.padding, act=self.act, residual_q=residual,
+            res_scale=self.res_scale if residual is not None else 1.0,
+            out_scale=self.out_scale)
+
+    def extra_repr(self):
+        return (f"{self.cin}->{self.cout} k{self.kernel} s{self.stride} "
+                f"p{self.padding} act={self.act} "
+                f"out={'bf16' if self.out_scale is None else 'e4m3'}")
+
+    def flops_per_pixel(self):
+        return 2 * self.kernel * self.kernel * self.cin * self.cout
+
+
 class AddAct(nn.Module):
     """Residual add + activation — the reference's `add_N` cut layers
     (test/test.py:18) with the ReLU that follows them fused in."""

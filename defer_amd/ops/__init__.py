@@ -535,6 +535,111 @@ def gconv2d_bn_act(x, w, scale=None, bias=None, stride=1, padding=1,
     return m.gconv2d_bn_act(x, w, scale, bias, stride, padding, code)
 
 
+_FP8 = torch.float8_e4m3fn
+_FP8_ACTS = ("none", "relu", "relu6")
+
+
+def quantize_fp8(x, scale, max_blocks=0):
+    """x / scale as OCP e4m3 (torch.float8_e4m3fn): byte for byte
+    (x.float() * inv).clamp(-448, 448).to(torch.float8_e4m3fn) with inv =
+    1 / scale rounded to fp32, round to nearest even, saturating. x is bf16
+    or fp32 with numel % 16 == 0; scale a positive host float (no sync). On
+    the GPU one HIP kernel (csrc/conv_fp8.hip); max_blocks caps its grid
+    (0 = policy)."""
+    if x.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"quantize_fp8: x must be bf16 or fp32, got "
+                         f"{x.dtype}")
+    if x.numel() % 16:
+        raise ValueError(f"quantize_fp8: needs numel % 16 == 0, got "
+                         f"{x.numel()}")
+    if not scale > 0.0:
+        raise ValueError(f"quantize_fp8: scale must be > 0, got {scale}")
+    m = _backend(x)
+    if m is None:
+        return _ref.quantize_fp8(x, 1.0 / scale)
+    return m.quantize_fp8(x, 1.0 / scale, max_blocks)
+
+
+def _check_conv_fp8(x, w, scale, bias, stride, padding, residual):
+    """The contract of csrc/conv_fp8.hip; the same refusals on every
+    device, each naming the value it refuses."""
+    for name, t in (("x_q", x), ("w_q", w), ("residual_q", residual)):
+        if t is not None and t.dtype != _FP8:
+            raise ValueError(f"conv2d_bn_act_fp8: {name} must be "
+                             f"torch.float8_e4m3fn, got {t.dtype}")
+    if x.dim() != 4 or w.dim() != 4:
+        raise ValueError(
+            f"conv2d_bn_act_fp8: x_q must be NHWC and w_q OHWI, got "
+            f"{x.dim()}-D and {w.dim()}-D")
+    cout, r, s, cin = w.shape
+    if x.shape[-1] != cin or cin % 16 or cout % 16:
+        raise ValueError(
+            f"conv2d_bn_act_fp8: needs Cin % 16 == 0 and Cout % 16 == 0 "
+            f"with x_q and w_q agreeing on Cin, got x_q {tuple(x.shape)} "
+            f"and w_q {tuple(w.shape)}")
+    if r != s:
+        raise ValueError(f"conv2d_bn_act_fp8: needs a square kernel, got "
+                         f"{r}x{s}")
+    if stride not in (1, 2):
+        raise ValueError(f"conv2d_bn_act_fp8: needs stride 1 or 2, got "
+                         f"{stride}")
+    if not 0 <= padding <= r // 2:
+        raise ValueError(f"conv2d_bn_act_fp8: needs 0 <= padding <= "
+                         f"{r // 2}, got {padding}")
+    for name, t in (("scale", scale), ("bias", bias)):
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32
+                or t.device != x.device or t.numel() != cout):
+            raise ValueError(
+                f"conv2d_bn_act_fp8: {name} must be an fp32 tensor of "
+                f"{cout} values on {x.device}")
+    if residual is not None:
+        oh = (x.shape[1] + 2 * padding - r) // stride + 1
+        ow = (x.shape[2] + 2 * padding - s) // stride + 1
+        if tuple(residual.shape) != (x.shape[0], oh, ow, cout):
+            raise ValueError(
+                f"conv2d_bn_act_fp8: residual_q must have the output's "
+                f"shape {(x.shape[0], oh, ow, cout)}, got "
+                f"{tuple(residual.shape)}")
+
+
+def conv2d_bn_act_fp8(x_q, w_q, scale, bias, stride=1, padding=0,
+                      act="none", residual_q=None, res_scale=1.0,
+                      out_scale=None, max_blocks=0):
+    """Convolution on e4m3 bytes with fp32 accumulation, NHWC x_q and OHWI
+    w_q (torch.float8_e4m3fn), for output channel c in fp32:
+
+        v = act(acc * scale[c] + bias[c] + res_scale * float(residual_q))
+
+    scale[c] carries the folded BN scale times the input's activation scale
+    times channel c's weight scale. out_scale=None returns bf16 (one
+    rounding of v); otherwise e4m3 of clamp(v / out_scale, -448, 448), round
+    to nearest even, with 1 / out_scale rounded to fp32 first. res_scale and
+    out_scale are host floats: no sync, capturable. act is "none", "relu" or
+    "relu6". On the GPU one HIP kernel on the fp8 MFMA (csrc/conv_fp8.hip)
+    for Cin % 16 == 0, Cout % 16 == 0, a square kernel, stride 1 or 2 and
+    padding <= R // 2; anything else raises, on the CPU too. Deterministic.
+    max_blocks caps the grid (0 = policy)."""
+    code = _act_code(act, _FP8_ACTS)
+    _check_conv_fp8(x_q, w_q, scale, bias, stride, padding, residual_q)
+    inv = None if out_scale is None else 1.0 / out_scale
+    m = _backend(x_q)
+    if m is None:
+        return _ref.conv2d_bn_act_fp8(x_q, w_q, scale, bias, stride, padding,
+                                      act, residual_q, res_scale, inv)
+    return m.conv2d_bn_act_fp8(x_q, w_q, scale, bias, residual_q, stride,
+                               padding, code, res_scale, inv, max_blocks)
+
+
+def conv_fp8_plan(x_shape, w_shape, stride=1, padding=0, max_blocks=0):
+    """What conv2d_bn_act_fp8 would launch for these NHWC / OHWI shapes,
+    without launching it: {"tile": "large" (128x128) or "small" (64x64),
+    "bm", "bn", "m_tiles", "n_tiles", "k_tiles", "grid", "lds_bytes",
+    "mfma": "fp8", or "bf16" for K < 128 (the bytes widened in registers)}.
+    Needs the built extension but no GPU."""
+    return dict(_built().conv_fp8_plan(list(x_shape), list(w_shape), stride,
+                                       padding, max_blocks))
+
+
 def conv_plan(x_shape, w_shape, stride=1, padding=1, residual=False,
               mode=None, max_blocks=0, variant=None):
     """What conv2d_bn_act (NHWC / OHWI shapes) or linear (2-D shapes) would

@@ -78,6 +78,32 @@ def conv2d_bn_act(
     return apply_act(y, act).to(x.dtype)
 
 
+def quantize_fp8(x, inv_scale):
+    """e4m3(clamp(x * inv_scale, -448, 448)), round to nearest even. The
+    clamp is the saturation: torch's cast alone gives NaN above 464."""
+    return (x.float() * inv_scale).clamp(-448.0, 448.0).to(
+        torch.float8_e4m3fn)
+
+
+def conv2d_bn_act_fp8(x_q, w_q, scale, bias, stride, padding, act,
+                      residual_q=None, res_scale=1.0, out_inv_scale=None):
+    """The arithmetic of csrc/conv_fp8.hip in fp32 torch: dequantise the
+    e4m3 bytes, conv, v = act(acc * scale + bias + res_scale * residual),
+    then e4m3(clamp(v * out_inv_scale, +-448)) or, with out_inv_scale None,
+    one bf16 rounding of v."""
+    xf = x_q.float().permute(0, 3, 1, 2)
+    wf = w_q.float().permute(0, 3, 1, 2)
+    y = F.conv2d(xf, wf, bias=None, stride=stride, padding=padding)
+    y = y * scale.float().view(1, -1, 1, 1) + bias.float().view(1, -1, 1, 1)
+    y = y.permute(0, 2, 3, 1)
+    if residual_q is not None:
+        y = y + res_scale * residual_q.float()
+    y = apply_act(y, act, known=("none", "relu", "relu6"))
+    if out_inv_scale is None:
+        return y.to(torch.bfloat16)
+    return quantize_fp8(y, out_inv_scale)
+
+
 def dwconv2d_bn_act(x, w, scale=None, bias=None, stride=1, padding=1,
                     act="none"):
     """Depthwise conv + (folded) batchnorm + activation: x [N, H, W, C],

@@ -20,7 +20,8 @@ CSRC = ROOT / "defer_amd" / "csrc"
 
 sources = [str(CSRC / f) for f in
            ["bindings.cpp", "conv.hip", "conv_ws.hip", "prebn.hip", "chain.hip", "stem_pool.hip", "elementwise.hip", "pool.hip", "dwconv.hip", "dwconv7.hip", "layernorm.hip", "gconv.hip", "se.hip", "attention.hip", "window_attention.hip",
-            "layout.hip", "codec.hip", "lz4.hip", "pack.hip", "conv_f32.hip", "ops_f32.hip"]
+            "layout.hip", "codec.hip", "lz4.hip", "pack.hip", "conv_f32.hip", "ops_f32.hip",
+            "conv_fp8.hip"]
            if (CSRC / f).exists()]
 
 setup(
