@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include "kernels.h"
+
 #define WAVE 64
 
 typedef __bf16 bf16;
@@ -37,16 +39,7 @@ __device__ __forceinline__ int cdiv(int a, int b) { return (a + b - 1) / b; }
 #define MFMA_BF16_16x16x32(a, b, c) \
     __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 
-// activation codes
-// (ACT_RELU6 is a runtime value of the depthwise and fp32 conv kernels and
-// of the bindings; the bf16 conv templates take ACT_RELU with a bound for
-// it, and ACT_NONE, ACT_RELU or ACT_HARDSWISH as their ACT)
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_RELU6 = 2, ACT_HARDSWISH = 3 };
-// the exact GELU of linear_gelu. Not a value of the ops' `act`: only the
-// GEMM-mode instantiations behind launch_gemm_gelu and launch_conv_f32's
-// caller in that binding name it.
-enum { ACT_GELU = 4 };
-
+// the activation codes ACT_* are in kernels.h, which host code can include
 // gelu(v) = 0.5 * v * (1 + erf(v / sqrt(2))), in this order everywhere
 // (ops/reference.py too); erff(v * 0.70710678f) is 1 in fp32 from about
 // v = 5.6, so gelu returns v bit for bit from there.

@@ -5,6 +5,17 @@
 
 #include <hip/hip_runtime.h>
 
+// Activation codes: the one C++ place, for the kernels (through common.h),
+// the launchers and the bindings; ops/__init__.py mirrors them by name.
+// ACT_RELU6 is a runtime value of the depthwise, grouped and fp32 conv
+// kernels and of the bindings; the bf16 conv templates take ACT_RELU with an
+// upper bound for it, and ACT_NONE, ACT_RELU or ACT_HARDSWISH as their ACT.
+enum { ACT_NONE = 0, ACT_RELU = 1, ACT_RELU6 = 2, ACT_HARDSWISH = 3 };
+// the exact GELU of linear_gelu. Not a value of the ops' `act`: only the
+// GEMM-mode instantiations behind launch_gemm_gelu and launch_conv_f32's
+// caller in that binding name it.
+enum { ACT_GELU = 4 };
+
 namespace defer_hip {
 
 // bf16 pointers are passed as void* across the host boundary.
@@ -142,7 +153,7 @@ struct ConvF32Params {
     int M, K, Cout;
     int H, W, Cin;
     int OH, OW, S, stride, pad;
-    int relu;           // an ACT_* of common.h, ACT_HARDSWISH included;
+    int relu;           // an ACT_* (above), ACT_HARDSWISH included;
                         // ACT_GELU from the linear_gelu binding alone
 };
 // tile: 0 = heuristic, 1 = 128x128, 2 = 128x64 (A/B measurement switch)
@@ -267,7 +278,7 @@ void launch_embed_tokens_f32(const float* x, const float* cls,
 // grouped 3x3 conv + folded BN + activation (gconv.hip), NHWC x and
 // [C][3][3][Cg] w, Cin == Cout == C, C % 16 == 0, C % Cg == 0, Cg in {4, 8,
 // 16, 32}, stride in {1, 2}, pad in {0, 1}; scale and bias non-null fp32[C];
-// act is an ACT_* of common.h. zbuf: >= 16 B of zeros (the bf16 kernel reads
+// act is an ACT_* (above). zbuf: >= 16 B of zeros (the bf16 kernel reads
 // padding from it). x and y have fewer than 2^31 elements.
 void launch_gconv(const void* x, const void* w, const float* scale,
                   const float* bias, const void* zbuf, void* y, int NB, int H,

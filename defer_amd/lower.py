@@ -58,7 +58,7 @@ fused only through intermediates with exactly one consumer, and the fused
 node takes the name of the pattern's last node, so a cut name that refers
 to the pattern's output stays valid. A pattern is lowered only where the
 HIP op accepts its shape in both compute dtypes (the `TORCH_CHECK`s of
-`csrc/bindings.cpp`); anything else stays an island, with the reason
+`csrc/entry_*.cpp`); anything else stays an island, with the reason
 recorded in the `TorchIsland` that wraps it.
 
 In-place ops: torch writes an in-place ReLU, ReLU6, Hardswish or `a += b`
@@ -85,7 +85,7 @@ from defer_amd.models import layers as L
 
 NCHW, NHWC = "nchw", "nhwc"
 
-# what the HIP ops take in BOTH compute dtypes (csrc/bindings.cpp): the
+# what the HIP ops take in BOTH compute dtypes (csrc/entry_*.cpp): the
 # bf16 kernels move 8 elements per lane and the fp32 ones 4, so the bf16
 # rule covers both, except for the conv's Cout and the linear's N, which
 # only the fp32 kernels constrain

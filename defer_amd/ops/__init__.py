@@ -83,7 +83,7 @@ def _stats(name):
     return dict(getattr(_built(), name)())
 
 
-# activation names -> the codes of the bindings (ACT_* of csrc/common.h)
+# activation names -> the codes of the bindings (ACT_* of csrc/kernels.h)
 _ACT_CODES = {"none": 0, "relu": 1, "relu6": 2, "hardswish": 3}
 _RELU_OR_NONE = ("relu", "none")
 _SE_GATES = ("hardsigmoid",)

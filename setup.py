@@ -18,11 +18,19 @@ from torch.utils.cpp_extension import BuildExtension, CUDAExtension  # noqa: E40
 ROOT = Path(__file__).parent
 CSRC = ROOT / "defer_amd" / "csrc"
 
+# A source that is missing fails the build here, not the import later. The
+# build compiles the units in name order whatever the order here: the host
+# units are named entry_* so that conv.hip, whose device compile is the
+# longest unit, still starts with the first jobs.
 sources = [str(CSRC / f) for f in
-           ["bindings.cpp", "conv.hip", "conv_ws.hip", "prebn.hip", "chain.hip", "stem_pool.hip", "elementwise.hip", "pool.hip", "dwconv.hip", "dwconv7.hip", "layernorm.hip", "gconv.hip", "se.hip", "attention.hip", "window_attention.hip",
-            "layout.hip", "codec.hip", "lz4.hip", "pack.hip", "conv_f32.hip", "ops_f32.hip",
-            "conv_fp8.hip"]
-           if (CSRC / f).exists()]
+           ["conv.hip", "bindings.cpp", "entry_util.cpp", "entry_conv.cpp",
+            "entry_dwconv.cpp", "entry_pointwise.cpp", "entry_attention.cpp",
+            "entry_fp8.cpp", "entry_codec.cpp", "conv_ws.hip", "prebn.hip",
+            "chain.hip", "stem_pool.hip", "elementwise.hip", "pool.hip",
+            "dwconv.hip", "dwconv7.hip", "layernorm.hip", "gconv.hip",
+            "se.hip", "attention.hip", "window_attention.hip", "layout.hip",
+            "codec.hip", "lz4.hip", "pack.hip", "conv_f32.hip", "ops_f32.hip",
+            "conv_fp8.hip"]]
 
 setup(
     name="defer_amd",
